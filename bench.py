@@ -9,7 +9,12 @@ Inputs (points, y = f_ackley(x)) are resident in HBM before the timed region; GP
 initial hyper-parameters and all caches are dropped at the start of every step.
 value = (shifts * n * world_size) / (max-over-ranks seconds per step).
 
-Extra JSON keys: "roofline" for the dominant kernel (priced on the rocprofv3 kernel-trace average of this
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and prints the headline
+line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...); `--dump-outputs DIR` also writes what the last
+timed step computed (fitted raw parameters, post_mean, post_var) as DIR/<name>.npy.  Everything below is measured
+only with `--full`.
+
+Extra JSON keys (--full): "roofline" for the dominant kernel (priced on the rocprofv3 kernel-trace average of this
 command committed under profiles/; its launches also timed live on the device clock, fgp_nll_desc.stamps,
 and with HIP events, both reported beside it),
 "cpu_baseline" (the oracle = torch-CPU restatement of the reference, rank 0 at N=1, bounded sample),
@@ -51,6 +56,15 @@ def parse():
     p.add_argument("--fit-iters", type=int, default=50)
     p.add_argument("--n-mean", type=int, default=256)
     p.add_argument("--n-var", type=int, default=8)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything beside the headline: the eager rate of the same "
+                        "steps, per-phase and per-kernel (roofline) figures, the CPU baseline, the secondary BASELINE "
+                        "configs, the paper's and the multitask examples' per-step timings (each can be switched off "
+                        "with its --no-... option)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="directory: after the timed steps write what the last timed step computed -- the fitted raw "
+                        "parameters [P, 2 + d], post_mean [P, n_mean] and post_var [P, n_var] of the rank's shifts -- as "
+                        "DIR/<name>.npy (float64; with N > 1 ranks DIR/rank<r>_<name>.npy)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--sequential", dest="batched", action="store_false",
                    help="fit and predict the shifts one by one (default: one GPBatch over all shifts)")
@@ -153,11 +167,14 @@ def step_batched(sh, args, xm, xv, store_loss_hist=False):
 
 
 def step_sequential(sh, args, xm, xv):
+    """The same step, one GP after the other; returns the per-GP lists (fit data, post_mean [N], post_var [N])."""
     sh.reset()
+    data, pm, pv = [], [], []
     for gp in sh.gps:
-        gp.fit(iterations=args.fit_iters, stop_crit_wait_iterations=args.fit_iters + 1, verbose=0)
-        gp.post_mean(xm)
-        gp.post_var(xv)
+        data.append(gp.fit(iterations=args.fit_iters, stop_crit_wait_iterations=args.fit_iters + 1, verbose=0))
+        pm.append(gp.post_mean(xm))
+        pv.append(gp.post_var(xv))
+    return data, pm, pv
 
 
 class SingleGP(object):
@@ -505,9 +522,10 @@ def graph_phases(F, sg, args, xm, xv, device, reps=5):
     return {k: sorted(r[i] for r in rows)[reps // 2] for i, k in enumerate(keys)}
 
 
-def capture_fn(fn):
+def capture_fn(fn, outputs=None):
     """fn() (returning a tuple of device tensors) captured once into a hipGraph; (graph, info).  The replay's
-    outputs must equal an eager call's bit for bit, else (None, info) and the caller times the eager calls."""
+    outputs must equal an eager call's bit for bit, else (None, info) and the caller times the eager calls.
+    outputs: a list that receives the graph's own output tensors (every replay rewrites them in place)."""
     info = {"used": False}
     try:
         s = torch.cuda.Stream()
@@ -534,6 +552,8 @@ def capture_fn(fn):
             info["error"] = "replay differs from the eager call"
             return None, info
         info.update({"used": True, "check": "replay == eager call (post_mean, post_var bit for bit)"})
+        if outputs is not None:
+            outputs.extend(out)
         return g, info
     except Exception as e:          # capture not possible here: time the eager enqueue
         import traceback
@@ -543,12 +563,28 @@ def capture_fn(fn):
         return None, info
 
 
-def capture_step(sh, args, xm, xv):
+def capture_step(sh, args, xm, xv, outputs=None):
     """The whole batched step (data re-ingest + parameter reset, ytilde, spectra, 50 fit iterations, coefficients,
     post_mean, post_var) captured once into a hipGraph and replayed per timed step: the same device work,
     without the host's per-launch Python.  Checked on the spot: a replay's post_mean / post_var equal an eager
     step's bit for bit, else the eager loop is timed (graph_info says why)."""
-    return capture_fn(lambda: step_batched(sh, args, xm, xv)[1:])
+    return capture_fn(lambda: step_batched(sh, args, xm, xv)[1:] + (sh.batch.raw(),), outputs)
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, rank, world, arrays):
+    """--dump-outputs: the named device tensors as float64 <name>.npy under `path` (rank<r>_<name>.npy when
+    N > 1), at most DUMP_MAX_BYTES per rank in all: an array over its equal share of that is written as a fixed
+    (seed 0) sorted sample of its flattened elements."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // (8 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float64).numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, ("rank%d_" % rank if world > 1 else "") + name + ".npy"), a)
 
 
 def main():
@@ -582,14 +618,14 @@ def main():
     xv = torch.rand((args.n_var, d), generator=g).to(device)
 
     def step():
-        (step_batched if args.batched else step_sequential)(shifts, args, xm, xv)
+        return (step_batched if args.batched else step_sequential)(shifts, args, xm, xv)
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    graph, graph_info = None, {"used": False}
+    graph, graph_info, graph_out = None, {"used": False}, []
     if args.graph and args.batched:
-        graph, graph_info = capture_step(shifts, args, xm, xv)
+        graph, graph_info = capture_step(shifts, args, xm, xv, graph_out)
     # two device-clock stamp kernels bracket the timed loop (outside the timed interval): the first two
     # k_clock_stamp launches of a rocprofv3 --kernel-trace of this command mark the timed region, whose launches
     # tools/timed_region_stats.py averages (the graph replays' per-kernel durations the roofline is priced on)
@@ -599,12 +635,13 @@ def main():
     torch.cuda.synchronize()
     if dist:
         tdist.barrier()
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
         if graph is not None:
             graph.replay()
         else:
-            step()
+            last = step()
     torch.cuda.synchronize()
     if dist:
         tdist.barrier()
@@ -615,7 +652,15 @@ def main():
     giveup_err = replay_giveup_error(F, gu0)
     if giveup_err:
         raise RuntimeError("timed steps invalid: " + giveup_err)
-    if graph is not None:
+    if args.dump_outputs:
+        if graph is not None:
+            pm, pv, raw = graph_out      # the graph's output tensors: the last replay's results
+        else:
+            pm, pv, raw = last[1], last[2], shifts.batch.raw()
+            if not args.batched:
+                pm, pv = torch.stack(pm), torch.stack(pv)
+        dump_outputs(args.dump_outputs, rank, world, {"raw": raw, "post_mean": pm, "post_var": pv})
+    if graph is not None and args.full:
         # the same steps enqueued eagerly (host-side Python per launch), for comparison
         torch.cuda.synchronize()
         gs0 = fit_graph_stats(F)
@@ -634,6 +679,25 @@ def main():
         os.makedirs(args.dump, exist_ok=True)
         np.savez(os.path.join(args.dump, "rank%d.npz" % rank), seeds=np.array(shard_seeds(rank, world, args.shifts)),
                  raw=shifts.batch.raw().cpu().numpy(), post_mean=pm.cpu().numpy(), post_var=pv.cpu().numpy())
+    head = {"metric": "GP fit+predict points/sec at n=2^20 fp64; achieved HBM GB/s vs roofline",
+            "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": sec_step * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f64", "data": "synthetic (f_ackley on shifted rank-1 lattices)",
+            "config": {"workload": "C4: FastGPLattice n=2^%d d=%d, %d random shifts per GPU, fit %d Rprop iters + "
+                                   "post_mean N=%d + post_var N=%d per shift" %
+                                   (args.log2n, d, args.shifts, args.fit_iters, args.n_mean, args.n_var),
+                       "global_shifts": args.shifts * world, "parallelism": "replicas%d" % world}}
+    value_from = ("hipGraph replay of the whole step (captured once, replay checked bit-identical to an eager step)"
+                  if graph is not None else "eager enqueue of every step")
+    if not args.full:
+        # a plain run: the headline alone
+        if rank == 0:
+            head["timing"] = {"value_from": value_from}
+            head["graph"] = graph_info
+            print(json.dumps(head))
+        if dist:
+            tdist.destroy_process_group()
+        return
     phases = phase_breakdown(shifts, args.fit_iters, xm, xv)
     n_, variant, us, us_ev, t_iter, khz = roofline_fit_kernels(F, shifts, args.fit_iters)
     parts_array = variant not in ("spectral", "spectral_fused", "re")
@@ -717,22 +781,14 @@ def main():
     if args.multitask and world == 1:
         multitask = multitask_configs(F, device)
     if rank == 0:
-        out = {"metric": "GP fit+predict points/sec at n=2^20 fp64; achieved HBM GB/s vs roofline",
-               "value": value, "unit": "points/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-               "ms_per_step": sec_step * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-               "dtype": "f64", "data": "synthetic (f_ackley on shifted rank-1 lattices)",
-               "config": {"workload": "C4: FastGPLattice n=2^%d d=%d, %d random shifts per GPU, fit %d Rprop iters + "
-                                      "post_mean N=%d + post_var N=%d per shift" %
-                                      (args.log2n, d, args.shifts, args.fit_iters, args.n_mean, args.n_var),
-                          "global_shifts": args.shifts * world, "parallelism": "replicas%d" % world},
-               "timing": {"value_from": "hipGraph replay of the whole step (captured once, replay checked bit-identical "
-                                        "to an eager step)" if graph is not None else "eager enqueue of every step",
-                          "value_eager": (args.shifts * n * world / (graph_info["eager_ms_per_step"] * 1e-3)
-                                          if graph is not None else value),
-                          "ms_per_step_eager": graph_info.get("eager_ms_per_step", sec_step * 1e3)},
-               "roofline": roof, "roofline_predict": roof_pm,
-               "cpu_baseline": cpu, "phases_ms": phases, "secondary": secondary,
-               "paper": paper, "multitask": multitask, "graph": graph_info}
+        out = dict(head)
+        out.update({"timing": {"value_from": value_from,
+                               "value_eager": (args.shifts * n * world / (graph_info["eager_ms_per_step"] * 1e-3)
+                                               if graph is not None else value),
+                               "ms_per_step_eager": graph_info.get("eager_ms_per_step", sec_step * 1e3)},
+                    "roofline": roof, "roofline_predict": roof_pm,
+                    "cpu_baseline": cpu, "phases_ms": phases, "secondary": secondary,
+                    "paper": paper, "multitask": multitask, "graph": graph_info})
         print(json.dumps(out))
     if dist:
         tdist.destroy_process_group()

@@ -102,6 +102,25 @@ def test_gpus_flag_starts_a_launcher_child(monkeypatch, capsys):
     assert capsys.readouterr().out.strip() == '{"metric": "m", "n_gpus": 3}'
 
 
+def test_dump_outputs_writes_float64_npy_within_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): <name>.npy in float64, whole when it fits its share of the byte cap, else
+    the same seeded sample of its elements in every run; rank<r>_<name>.npy when there are several ranks."""
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2 * 8 * 100)           # two arrays: 100 elements each
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4) / 7
+    big = torch.arange(1000, dtype=torch.float32)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), 0, 1, {"small": small, "big": big})
+    a_small, a_big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert a_small.dtype == np.float64 and np.array_equal(a_small, small.numpy())
+    assert a_big.dtype == np.float64 and a_big.shape == (100,)
+    assert (np.diff(a_big) > 0).all() and 0 <= a_big[0] and a_big[-1] <= 999 and (a_big == np.round(a_big)).all()
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "big.npy"))
+    bench.dump_outputs(str(tmp_path / "c"), 1, 2, {"small": small})
+    assert np.array_equal(np.load(tmp_path / "c" / "rank1_small.npy"), small.numpy())
+
+
 def test_c4_fixture_inputs_are_the_benched_shifts():
     """tests/golden/c4_m20_d5_it50.npz (the real reference over bench.py's exact C4 work) holds the inputs bench.py
     generates: the shift seeds of rank 0, the package's default generating vector, the shifts of seqs.Lattice

@@ -121,8 +121,8 @@ def test_bench_gpus_2_runs_two_ranks(tmp_path):
     import sys
     import numpy as np
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--log2n", "14", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-paper", "--no-multitask",
-              "--fit-iters", "10", "--n-mean", "8", "--n-var", "2"]
+    common = ["--full", "--log2n", "14", "--steps", "1", "--warmup", "1", "--no-secondary", "--no-paper",
+              "--no-multitask", "--fit-iters", "10", "--n-mean", "8", "--n-var", "2"]
     env = dict(os.environ, FGP_BENCH_DEVICE="0", FGP_BENCH_BACKEND="gloo", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
     runs = {}
@@ -146,6 +146,46 @@ def test_bench_gpus_2_runs_two_ranks(tmp_path):
         assert list(got["seeds"]) == [1000 + 2 * r, 1001 + 2 * r]
         for k in ("raw", "post_mean", "post_var"):
             assert np.array_equal(got[k], one[k][2 * r:2 * r + 2]), (r, k)
+
+
+@pytest.mark.parametrize("extra", [[], ["--no-graph"]], ids=["graph", "eager"])
+def test_plain_run_prints_the_headline_and_dumps_the_last_timed_step(tmp_path, monkeypatch, capsys, extra):
+    """A plain `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (bench.main in this process, a small C4
+    shape): one JSON line with the headline keys and none of the --full measurements, steps = K, value =
+    shifts * n / (ms_per_step / 1e3); DIR/{raw,post_mean,post_var}.npy in float64, finite, of the step's shapes;
+    with --no-graph equal, bit for bit, to what bench.step_batched returns for the same shifts and test points."""
+    import json
+    import sys
+    import numpy as np
+    m, d, P, its = 17, 5, 2, 5
+    out = tmp_path / "out"
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2n", str(m),
+                                      "--shifts", str(P), "--fit-iters", str(its), "--n-mean", "8", "--n-var", "2",
+                                      "--dump-outputs", str(out)] + extra)
+    bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["unit"] == "points/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["metric"].startswith("GP fit+predict points/sec") and line["steps"] == 2 and line["n_gpus"] == 1
+    assert line["ms_per_step"] > 0
+    assert abs(line["value"] - P * 2 ** m / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    assert line["graph"]["used"] is (not extra), line["graph"]
+    for k in ("roofline", "roofline_predict", "cpu_baseline", "phases_ms", "secondary", "paper", "multitask"):
+        assert k not in line
+    dev = torch.device(DEV, 0)
+    sh = bench.Shifts(F, d, 2 ** m, bench.shard_seeds(0, 1, P), dev)
+    g = torch.Generator().manual_seed(17)
+    xm, xv = torch.rand((8, d), generator=g).to(dev), torch.rand((2, d), generator=g).to(dev)
+    _, pm, pv = bench.step_batched(sh, argparse.Namespace(fit_iters=its), xm, xv)
+    want = {"raw": sh.batch.raw(), "post_mean": pm, "post_var": pv}
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in want)
+    for k, v in want.items():
+        got = np.load(out / (k + ".npy"))
+        assert got.dtype == np.float64 and got.shape == tuple(v.shape) and np.isfinite(got).all(), k
+        if extra:       # the eager path: the same step; (the replayed outputs are the graph's own tensors)
+            assert np.array_equal(got, v.cpu().numpy()), k
 
 
 # The exact benched C4 work (n = 2^20, d = 5, alpha = 2, nugget 1e-8, 50 Rprop iterations with early stopping off,
