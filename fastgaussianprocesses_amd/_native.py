@@ -12,9 +12,10 @@ import torch
 
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
 LIB_PATH = os.environ.get("FGP_LIB_PATH") or os.path.join(_LIB_DIR, "libfgp_hip.so")   # override: experiments
-ABI_VERSION = 18
+ABI_VERSION = 19
 MT_MAX_TASKS = 16
 MAX_D = 8
+WIDE_MAX_D = 64                # the fgp_wide_* entry points: MAX_D < d <= WIDE_MAX_D
 PARTS_ARRAY = 0
 PARTS_LATTICE = 1
 
@@ -177,6 +178,17 @@ _SIGNATURES = {
     "fgp_spec_basis_work": [_c_int, _c_int, _c_int, _c_pl],
     "fgp_spec_basis_gen": [_c_pl, _c_int, _c_int, _c_int, _c_pd, _c_vp, _c_vp, _c_i64, _c_vp],
     "fgp_inv_eig": [_c_int, _c_vp, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp],
+    # ABI 19: wide inputs (MAX_D < d <= WIDE_MAX_D)
+    "fgp_wide_lattice_points": [_c_pl, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp],
+    "fgp_wide_lattice_parts": [_c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_pi, _c_pd, _c_vp, _c_vp],
+    "fgp_wide_net_parts": [_c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_vp, _c_vp, _c_vp],
+    "fgp_wide_k1": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp],
+    "fgp_wide_k1_bwd": [_c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp],
+    "fgp_wide_k1_bwd_work": [_c_i64, _c_int, _c_int, _c_pl],
+    "fgp_wide_kernel_rows": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_vp, _c_int, _c_vp,
+                             _c_vp],
+    "fgp_wide_post_mean": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_vp, _c_int, _c_vp,
+                           _c_i64, _c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp],
 }
 
 

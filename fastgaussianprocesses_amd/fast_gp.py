@@ -510,6 +510,14 @@ class AbstractFastGP(torch.nn.Module):
         """k1 = scale * prod_j(1 + l_j parts_j)  -> [*param_batch, n] (abstract_fast_gp.py:181-191)."""
         parts = self._k1parts(n) if parts is None else parts
         ls = self.lengthscales
+        if self.d > _native.MAX_D and ops.wide_fused():
+            # wide inputs: fgp_wide_k1 over the parameter rows (and fgp_wide_k1_bwd under autograd, which then chains
+            # through the transforms and broadcasting of scale / lengthscales) -- no [*lb, d, n] temporary
+            s = self.scale
+            rows = tuple(torch.broadcast_shapes(s.shape[:-1], ls.shape[:-1]))
+            k1 = ops.wide_k1(self._FAMILY, parts.contiguous(), s.expand(rows + (1,)).reshape(-1),
+                             ls.expand(rows + (self.d,)).reshape(-1, self.d))
+            return k1.reshape(rows + (parts.shape[-1],))
         factors = 1 + ls[..., :, None] * parts          # [*lb, d, n]
         return self.scale * factors.prod(-2)
 
@@ -1608,8 +1616,11 @@ class FastGPLattice(AbstractFastGP):
     def _parts_gen(self, n):
         """Regenerate the parts in the fused kernels (FGP_PARTS_LATTICE) when the points are this
         package's natural-order Lattice: bit-identical to the parts array, without its 2 x 8nd bytes of
-        HBM reads per fit iteration.  FGP_PARTS_GEN=0 disables it."""
+        HBM reads per fit iteration.  FGP_PARTS_GEN=0 disables it.  None for d > 8: the regenerating descriptors
+        are FGP_MAX_D-sized."""
         if os.environ.get("FGP_PARTS_GEN", "1") == "0" or not isinstance(self.seq, _seqs.Lattice):
+            return None
+        if self.d > _native.MAX_D:
             return None
         memo = getattr(self, "_pgen_memo", None)      # (a function of the point set and n only)
         if memo is not None and memo[0] == n and memo[1] is self.seq:

@@ -12,6 +12,7 @@ fast_gp_digital_net_b2.py:226):
 all differentiable (backward = the exact adjoint transform, real part for real inputs).
 With stable=True the mean-centring of AbstractFastGP.ft/ift happens inside the kernels.
 """
+import ctypes
 import functools
 import math
 import os
@@ -24,6 +25,11 @@ from . import _native as N
 
 LATTICE = 0
 NET = 1
+
+
+def _wide(d):
+    """d > 8: the fgp_wide_* entry points (9 <= d <= 64; include/fgp_hip.h, ABI 19) instead of the d <= 8 ones."""
+    return int(d) > N.MAX_D
 
 
 def require_device(t, what):
@@ -355,7 +361,8 @@ def lattice_parts(x, z, alphas, out=None):
     if out is None:
         out = torch.empty((d, n), dtype=torch.float64, device=x.device)
     assert out.shape == (d, n) and out.is_contiguous() and out.dtype == torch.float64
-    N.call("fgp_lattice_parts", N.ptr(x), x.stride(0), N.ptr(z), n, d, N.int_array([2 * a for a in alphas]),
+    N.call("fgp_wide_lattice_parts" if _wide(d) else "fgp_lattice_parts", N.ptr(x), x.stride(0), N.ptr(z), n, d,
+           N.int_array([2 * a for a in alphas]),
            N.double_array([lattice_coefficient(a) for a in alphas]), N.ptr(out), _stream(x))
     return out
 
@@ -368,7 +375,8 @@ def lattice_points(z, shift, n_min, n_max, device=None):
     shift = shift.contiguous()
     d = shift.numel()
     x = torch.empty((n_max - n_min, d), dtype=torch.float64, device=shift.device)
-    N.call("fgp_lattice_points", N.int64_array(z), N.ptr(shift), int(n_min), int(n_max), d, N.ptr(x), _stream(shift))
+    N.call("fgp_wide_lattice_points" if _wide(d) else "fgp_lattice_points", N.int64_array(z), N.ptr(shift), int(n_min),
+           int(n_max), d, N.ptr(x), _stream(shift))
     return x
 
 
@@ -412,8 +420,70 @@ def net_parts(xb, z, t, out=None, alphas=None):
         out = torch.empty((d, n), dtype=torch.float64, device=xb.device)
     assert out.shape == (d, n) and out.is_contiguous() and out.dtype == torch.float64
     order = N.int_array([int(a) for a in alphas]) if alphas is not None else None
-    N.call("fgp_net_parts", N.ptr(xb), xb.stride(0), N.ptr(z), n, d, int(t), order, N.ptr(out), _stream(xb))
+    N.call("fgp_wide_net_parts" if _wide(d) else "fgp_net_parts", N.ptr(xb), xb.stride(0), N.ptr(z), n, d, int(t), order,
+           N.ptr(out), _stream(xb))
     return out
+
+
+# ------------------------------------------------------------------------------------- wide first column
+def wide_fused():
+    """FGP_WIDE_FUSED=0 keeps the torch formulation scale * (1 + ls[..., None] * parts).prod(-2) of the first-column
+    kernel at d > 8 (A/B runs, tests); default: fgp_wide_k1 / fgp_wide_k1_bwd."""
+    return os.environ.get("FGP_WIDE_FUSED", "1")[:1] != "0"
+
+
+def wide_k1_raw(parts, scale_rows, ls_rows):
+    """k1[g, i] = scale_rows[g] prod_j (1 + ls_rows[g, j] parts[j, i]) -> [G, n] (fgp_wide_k1); parts [d, n], d > 8."""
+    require_device(parts, "wide_k1")
+    d, n = parts.shape
+    G = scale_rows.numel()
+    assert parts.dtype == torch.float64 and parts.is_contiguous() and ls_rows.shape == (G, d)
+    sc = scale_rows.detach().to(torch.float64).reshape(G).contiguous()
+    ls = ls_rows.detach().to(torch.float64).contiguous()
+    k1 = torch.empty((G, n), dtype=torch.float64, device=parts.device)
+    N.call("fgp_wide_k1", N.ptr(parts), n, d, N.ptr(sc), N.ptr(ls), G, N.ptr(k1), _stream(parts))
+    return k1
+
+
+def wide_k1_bwd_raw(parts, scale_rows, ls_rows, u):
+    """(dL/dscale_rows [G], dL/dls_rows [G, d]) from u = dL/dk1 [G, n] (fgp_wide_k1_bwd: leave-one-out products,
+    fixed-order sums)."""
+    d, n = parts.shape
+    G = scale_rows.numel()
+    sc = scale_rows.detach().to(torch.float64).reshape(G).contiguous()
+    ls = ls_rows.detach().to(torch.float64).contiguous()
+    u = resolved(u.to(torch.float64)).reshape(G, n).contiguous()
+    ds = torch.empty((G,), dtype=torch.float64, device=parts.device)
+    dl = torch.empty((G, d), dtype=torch.float64, device=parts.device)
+    wlen = ctypes.c_int64(0)
+    N.call("fgp_wide_k1_bwd_work", n, d, G, ctypes.byref(wlen))
+    work = torch.empty((wlen.value,), dtype=torch.float64, device=parts.device)
+    N.call("fgp_wide_k1_bwd", N.ptr(parts), n, d, N.ptr(sc), N.ptr(ls), G, N.ptr(u), N.ptr(ds), N.ptr(dl), N.ptr(work),
+           _stream(parts))
+    return ds, dl
+
+
+class _WideK1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, parts, scale_rows, ls_rows):
+        ctx.save_for_backward(parts, scale_rows, ls_rows)
+        return wide_k1_raw(parts, scale_rows, ls_rows)
+
+    @staticmethod
+    def backward(ctx, u):
+        parts, scale_rows, ls_rows = ctx.saved_tensors
+        ds, dl = wide_k1_bwd_raw(parts, scale_rows, ls_rows, u)
+        return None, ds.reshape(scale_rows.shape), dl
+
+
+def wide_k1(family, parts, scale_rows, ls_rows):
+    """First-column kernel of G hyper-parameter rows over one parts array [d, n], d > 8 (abstract_fast_gp.py:181-191;
+    the same formula for both families): k1 [G, n], differentiable with respect to the NATURAL scale rows [G] and
+    lengthscale rows [G, d] -- torch chains on through the parameter transforms and broadcasting -- without a
+    [G, d, n] temporary or a prod backward (fgp_wide_k1 / fgp_wide_k1_bwd)."""
+    if torch.is_grad_enabled() and (scale_rows.requires_grad or ls_rows.requires_grad):
+        return _WideK1.apply(parts, scale_rows, ls_rows)
+    return wide_k1_raw(parts, scale_rows, ls_rows)
 
 
 # ------------------------------------------------------------------------------------- prediction
@@ -453,21 +523,23 @@ def post_mean_matfree(family, xt, z_dn, hyp, coeffs, alphas=None, tbits=0, chunk
         coeffs = coeffs.contiguous()
     out = torch.empty((B, Nt), dtype=torch.float64, device=xt.device)
     order, coef = _pred_args(family, alphas, d)
+    # d > 8: fgp_wide_post_mean, the same convention with d * Nt more scratch (the test points dimension-major)
+    entry, xtra = ("fgp_wide_post_mean", d * Nt) if _wide(d) else ("fgp_post_mean", 0)
     if Gk == B and B > 4:
         # every output with its own hyper-parameters (C5 per-output): ONE launch over the blocks of 4 outputs
         # (fgp_post_mean, ABI 16) instead of one per block -- no launch gaps, the rounds of resident workgroups filled
         if chunk is None:
             chunk = post_mean_chunk(n, Nt * (B // 4))
         nchunks = (n + chunk - 1) // chunk
-        work = torch.empty((nchunks * B * Nt,), dtype=torch.float64, device=xt.device)
+        work = torch.empty((nchunks * B * Nt + xtra,), dtype=torch.float64, device=xt.device)
         hyp_c = hyp.contiguous()
-        N.call("fgp_post_mean", family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, int(tbits), order, coef, N.ptr(hyp_c), B,
+        N.call(entry, family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, int(tbits), order, coef, N.ptr(hyp_c), B,
                N.ptr(coeffs), coeffs.stride(0), B, N.ptr(out), Nt, N.ptr(work), chunk, _stream(xt))
         return out
     if chunk is None:
         chunk = post_mean_chunk(n, Nt)
     nchunks = (n + chunk - 1) // chunk
-    work_all = torch.empty((nchunks * min(B, 4) * Nt,), dtype=torch.float64, device=xt.device)
+    work_all = torch.empty((nchunks * min(B, 4) * Nt + xtra,), dtype=torch.float64, device=xt.device)
     for b0 in range(0, B, 4):
         b1 = min(B, b0 + 4)
         if Gk == 1:
@@ -476,9 +548,9 @@ def post_mean_matfree(family, xt, z_dn, hyp, coeffs, alphas=None, tbits=0, chunk
             hyp_b = hyp[b0:b1]        # a view: no gather launch per block of 4 outputs
         else:
             hyp_b = hyp[torch.arange(b0, b1, device=hyp.device) % Gk]
-        work = work_all[:nchunks * (b1 - b0) * Nt]
+        work = work_all[:nchunks * (b1 - b0) * Nt + xtra]
         cb = coeffs[b0:b1]
-        N.call("fgp_post_mean", family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, int(tbits), order, coef, N.ptr(hyp_b),
+        N.call(entry, family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, int(tbits), order, coef, N.ptr(hyp_b),
                hyp_b.shape[0], N.ptr(cb), cb.stride(0) if cb.shape[0] > 1 else n, b1 - b0, N.ptr(out[b0:b1]),
                Nt, N.ptr(work), chunk, _stream(xt))
     return out
@@ -526,7 +598,7 @@ def kernel_rows(family, xt, z_dn, hyp, alphas=None, tbits=0):
     for t0 in range(0, Nt, 65535):
         t1 = min(Nt, t0 + 65535)
         sub = torch.empty((Gk, t1 - t0, n), dtype=torch.float64, device=xt.device) if Nt > 65535 else rows
-        N.call("fgp_kernel_rows", family, N.ptr(xt[t0:t1]), t1 - t0, N.ptr(z_dn), n, d, int(tbits), order, coef,
+        N.call("fgp_wide_kernel_rows" if _wide(d) else "fgp_kernel_rows", family, N.ptr(xt[t0:t1]), t1 - t0, N.ptr(z_dn), n, d, int(tbits), order, coef,
                N.ptr(hyp), Gk, N.ptr(sub), _stream(xt))
         if sub is not rows:
             rows[:, t0:t1] = sub

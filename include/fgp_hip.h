@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FGP_ABI_VERSION 18
+#define FGP_ABI_VERSION 19
 
 #define FGP_OK 0
 #define FGP_ERR_INVALID (-1)     /* bad argument (shape, stride, null pointer) */
@@ -137,6 +137,7 @@ int fgp_sum_sq(const void* x, int64_t x_row_stride, int kind, int64_t R, int64_t
 #define FGP_FAMILY_LATTICE 0 /* shift-invariant kernel on lattice points: bit-reversed FFT */
 #define FGP_FAMILY_NET 1     /* digitally-shift-invariant kernel on digital nets: FWHT */
 #define FGP_MAX_D 8
+#define FGP_WIDE_MAX_D 64    /* ABI 19: the fgp_wide_* entry points take FGP_MAX_D < d <= FGP_WIDE_MAX_D */
 
 /* Lattice first-column kernel parts (fastgps/fast_gp_lattice.py:263-273, beta=kappa=0):
  *   parts[j, i] = coef[j] * B_{order[j]}((x[i, j] - x[0, j]) % 1),   i < n, j < d.
@@ -470,7 +471,69 @@ int fgp_inv_eig(int family, const void* lam, const void* ytilde, int64_t yt_stri
 int fgp_kernel_rows(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int tbits,
                     const int* order, const double* coef, const double* hyp, int Gk, double* rows, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * ABI 19 -- wide inputs, FGP_MAX_D < d <= FGP_WIDE_MAX_D (9 .. 64 dimensions; the reference takes any d).
+ * Every entry point above that reads points, parts or kernel rows keeps its d <= FGP_MAX_D domain (and error);
+ * these are their counterparts with per-dimension tables of FGP_WIDE_MAX_D entries, the same per-factor
+ * arithmetic, and the first-column kernel with its adjoint for the reference's autograd fit loop
+ * (AbstractGP.fit, abstract_gp.py:241-296).  Each validates its arguments before any HIP call: d outside
+ * 9 .. 64, a null pointer or a negative size returns FGP_ERR_INVALID with a message, also without a device.
+ * ------------------------------------------------------------------------------------------- */
 
+/* fgp_lattice_points for wide d (seqs.Lattice / qmcpy Lattice, abstract_gp.py:307-309 -> util.py:17-48), bit-identical
+ * to the host generator: with bits = ceil(log2(n_max)),
+ *   x[i - n_min, j] = ((brev_bits(i) z[j] mod 2^bits) / 2^bits + shift[j]) % 1,   n_min <= i < n_max <= 2^30.
+ * z: host [d] int64, 0 < z[j] < 2^(53 - bits); shift: device [d] in [0, 1); x: device [n_max - n_min, d] row-major. */
+int fgp_wide_lattice_points(const int64_t* z, const double* shift, int64_t n_min, int64_t n_max, int d, double* x,
+                            void* stream);
+
+/* fgp_lattice_parts for wide d (fastgps/fast_gp_lattice.py:263-273, beta=kappa=0):
+ *   parts[j, i] = coef[j] * B_{order[j]}((x[i, j] - z[j]) % 1),  i < n, j < d;  order[j] in {2,4,6,8}.
+ * x: [n, d] float64, row stride x_row_stride; z: device [d]; order, coef: host [d]; parts: [d, n] float64. */
+int fgp_wide_lattice_parts(const double* x, int64_t x_row_stride, const double* z, int64_t n, int d, const int* order,
+                           const double* coef, double* parts, void* stream);
+
+/* fgp_net_parts for wide d (fastgps/fast_gp_digital_net_b2.py:274-301): parts[j, i] = the Walsh part of order
+ * order[j] (1..4; order = NULL: all 1) of xb[i, j] XOR z[j], as fgp_net_parts (orders 2..4: the restated series,
+ * parity unpinned at the qmcpy boundary).  xb: [n, d] int64 t-bit integers (row stride xb_row_stride); z: device [d]
+ * int64; order: host [d]; parts: [d, n] float64. */
+int fgp_wide_net_parts(const int64_t* xb, int64_t xb_row_stride, const int64_t* z, int64_t n, int d, int t,
+                       const int* order, double* parts, void* stream);
+
+/* First-column kernel of G hyper-parameter rows over ONE parts array (_kernel_from_parts, abstract_fast_gp.py:181-191):
+ *   k1[g, i] = scale[g] * prod_j (1 + ls[g, j] * parts[j, i]),   g < G, i < n  (product in ascending j).
+ * parts: [d, n]; scale: device [G], ls: device [G, d] (the NATURAL parameters, broadcast to rows by the caller);
+ * k1: [G, n].  Reads 8 d n bytes per block of 4 rows, writes 8 G n. */
+int fgp_wide_k1(const double* parts, int64_t n, int d, const double* scale, const double* ls, int G, double* k1,
+                void* stream);
+
+/* Adjoint of fgp_wide_k1 (what loss.backward() computes through _kernel_from_parts' prod, abstract_gp.py:294): with
+ * u[g, i] = dL/dk1[g, i] and f_gji = 1 + ls[g, j] parts[j, i],
+ *   dscale[g] = sum_i u[g, i] prod_j f_gji,
+ *   dls[g, j] = sum_i u[g, i] scale[g] parts[j, i] prod_{j' != j} f_gj'i
+ * -- the leave-one-out products from prefix / suffix products, never by dividing k1 by a factor (a factor can be
+ * zero or negative at large ls).  One pass over the parts per row; per-block partials and a fixed tree (bitwise
+ * reproducible, no atomics).  u: [G, n]; dscale: [G]; dls: [G, d]; work: device scratch of fgp_wide_k1_bwd_work
+ * doubles.  n >= 1. */
+int fgp_wide_k1_bwd(const double* parts, int64_t n, int d, const double* scale, const double* ls, int G, const double* u,
+                    double* dscale, double* dls, double* work, void* stream);
+int fgp_wide_k1_bwd_work(int64_t n, int d, int G, int64_t* len);
+
+/* fgp_kernel_rows for wide d: rows[g, t, i] = K_g(xt[t], z[:, i]), [Gk][N][n], N <= 65535 (the kmat of
+ * AbstractGP.post_var / post_cov, fastgps/abstract_gp.py:407-411,452-457; the kernel of abstract_fast_gp.py:192-196).
+ * Arguments as fgp_kernel_rows: hyp device [Gk, 1 + d] (scale, lengthscales); order / coef host [d]. */
+int fgp_wide_kernel_rows(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int tbits,
+                         const int* order, const double* coef, const double* hyp, int Gk, double* rows, void* stream);
+
+/* fgp_post_mean for wide d (AbstractGP.post_mean, fastgps/abstract_gp.py:352-380), matrix-free:
+ *   out[b, t] = sum_i K_g(xt[t], z[:, i]) coeffs[b, i],  g = b mod Gk.
+ * Arguments and the B / Gk convention as fgp_post_mean (1 <= B <= 4, or any B when Gk == B: blocks of 4 outputs in
+ * one launch, out_stride == N), except work: float64 scratch of ceil(n/chunk) * B * N + d * N entries (the chunk
+ * partials and the test points dimension-major). */
+int fgp_wide_post_mean(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int tbits,
+                       const int* order, const double* coef, const double* hyp, int Gk, const double* coeffs,
+                       int64_t coeff_stride, int B, double* out, int64_t out_stride, double* work, int64_t chunk,
+                       void* stream);
 
 
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):

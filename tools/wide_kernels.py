@@ -1,0 +1,94 @@
+"""The wide (d > 8) path alone, for timing and for `rocprofv3 --kernel-trace --stats` passes:
+
+    python tools/wide_kernels.py time [m]    # ms per MLL loss + gradient evaluation, FGP_WIDE_FUSED=1 vs 0
+                                             # (alternating), and ms per wide post_mean; one JSON line
+    python tools/wide_kernels.py trace [m]   # the fused evaluations and the post_mean only (kernel names k_wide_*)
+    python tools/wide_kernels.py trace0 [m]  # the evaluations with the torch formulation of k1 (FGP_WIDE_FUSED=0)
+
+d = 16, n = 2^m, m = 16 by default (lattice, alpha = 2, lengthscales linspace(0.05, 0.3, d)), one hyper-parameter row; post_mean at
+N = 4096 test points, one output.  Byte / operation models:
+    k_wide_k1       8 d n + 8 n        bytes
+    k_wide_k1_bwd   8 d n + 16 n       bytes  (parts + u read; the partials are d + 1 doubles per 256 points)
+    k_wide_post_mean  (4 d + 1) N n    FP64 lane-ops (per pair and dimension: t = |x - z|, u = t^2 - t, u^2 + c', the
+                                       product; + the accumulate), as k_post_mean's model
+"""
+import json
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import fastgaussianprocesses_amd as F  # noqa: E402
+from oracle.fgp_oracle import f_ackley  # noqa: E402
+
+D, M, NT = 16, 16, 4096
+VALU_PEAK = 3.93e13      # FP64 lane-ops / s
+
+
+def make():
+    torch.set_default_dtype(torch.float64)
+    gp = F.FastGPLattice(F.Lattice(D, seed=3), lengthscales=torch.linspace(0.05, 0.3, D), device="cuda")
+    gp.add_y_next(f_ackley(gp.get_x_next(2 ** M)))
+    return gp
+
+
+def evaluate(gp):
+    gp._cache = {k: v for k, v in gp._cache.items() if not k[2]}
+    loss, _, _, _ = gp._loss_generic("MLL", None, 1, 1)
+    loss.backward()
+    gp.raw_scale.grad = gp.raw_lengthscales.grad = None
+    return loss
+
+
+def timed(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / reps * 1e3
+
+
+def main():
+    global M
+    mode = sys.argv[1] if len(sys.argv) > 1 else "time"
+    M = int(sys.argv[2]) if len(sys.argv) > 2 else M
+    gp = make()
+    n = 2 ** M
+    xt = torch.rand((NT, D), generator=torch.Generator().manual_seed(5)).to("cuda")
+    with torch.no_grad():
+        gp.coeffs
+    if mode in ("trace", "trace0"):
+        os.environ["FGP_WIDE_FUSED"] = "1" if mode == "trace" else "0"
+        for _ in range(25):
+            evaluate(gp)
+        for _ in range(10 if mode == "trace" else 0):
+            gp.post_mean(xt)
+        torch.cuda.synchronize()
+        return
+    res = {"d": D, "n": n, "N": NT, "eval_ms": {"1": [], "0": []}}
+    for flag in ("1", "0"):
+        os.environ["FGP_WIDE_FUSED"] = flag
+        for _ in range(5):
+            evaluate(gp)
+    for _ in range(4):                      # alternate the two versions in one process
+        for flag in ("1", "0"):
+            os.environ["FGP_WIDE_FUSED"] = flag
+            res["eval_ms"][flag].append(round(timed(lambda: evaluate(gp), 50), 4))
+    os.environ["FGP_WIDE_FUSED"] = "1"
+    for _ in range(3):
+        gp.post_mean(xt)
+    pm = [round(timed(lambda: gp.post_mean(xt), 20), 4) for _ in range(3)]
+    res["post_mean_ms"] = pm
+    res["post_mean_valu_share_end_to_end"] = round((4 * D + 1) * NT * n / (min(pm) * 1e-3) / VALU_PEAK, 3)
+    res["k1_bytes"] = 8 * D * n + 8 * n
+    res["k1_bwd_bytes"] = 8 * D * n + 16 * n
+    res["post_mean_lane_ops"] = (4 * D + 1) * NT * n
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
