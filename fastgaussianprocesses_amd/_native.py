@@ -12,7 +12,7 @@ import torch
 
 _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib")
 LIB_PATH = os.environ.get("FGP_LIB_PATH") or os.path.join(_LIB_DIR, "libfgp_hip.so")   # override: experiments
-ABI_VERSION = 19
+ABI_VERSION = 20
 MT_MAX_TASKS = 16
 MAX_D = 8
 WIDE_MAX_D = 64                # the fgp_wide_* entry points: MAX_D < d <= WIDE_MAX_D
@@ -167,6 +167,7 @@ _SIGNATURES = {
     "fgp_mt_fit_work": [_P_MTFIT, _c_pl],
     "fgp_mt_fit_run": [_P_MTFIT, _c_int, _c_int, _c_int, _c_vp],
     "fgp_handoff_check": [_c_int, ctypes.POINTER(ctypes.c_ulonglong)],
+    "fgp_spec_geometry": [_P_NLL, _c_int, _c_pi],          # ABI 20: test hook, no HIP call
     "fgp_set_persist_poll_max": [_c_i64],
     "fgp_persist_giveups": [ctypes.POINTER(ctypes.c_ulonglong), _c_int],
     "fgp_fit_graph_stats": [ctypes.POINTER(ctypes.c_longlong)],

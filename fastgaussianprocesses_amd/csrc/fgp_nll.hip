@@ -1332,6 +1332,18 @@ __global__ __launch_bounds__(kWG) void k_fwd_rows_r2c_gen(GenSpec g, int log2n, 
 
 // ------------------------------------------------------------------------------------------------
 // host-side launch logic
+// The spectral fields of a desc whose loss, G, d and basis_stride are set: spec_geometry, then the alternative
+// losses' per-wave kernel (one problem per wave, 2 + 2 (2 + d) quantities per block).
+static void spec_setup(Nll& a, bool allow_tile) {
+  spec_geometry(a, allow_tile && a.loss == FGP_LOSS_MLL);
+  a.nq = 4 + a.d;
+  if (a.loss != FGP_LOSS_MLL) {
+    a.spec_ppw = 1;
+    a.spec_pg = a.G;
+    a.nq = 6 + 2 * a.d;
+  }
+}
+
 static int to_nll(const fgp_nll_desc* d, Nll& a) {
   if (!d) return set_error(kErrInvalid, "null nll desc");
   if (d->family != FGP_FAMILY_LATTICE && d->family != FGP_FAMILY_NET) return set_error(kErrInvalid, "bad family");
@@ -1430,13 +1442,7 @@ static int to_nll(const fgp_nll_desc* d, Nll& a) {
   }
   if (a.spec) {
     a.re = a.r2c = 0;
-    spec_geometry(a, a.loss == FGP_LOSS_MLL);
-    if (a.loss != FGP_LOSS_MLL) {
-      // the alternative losses' per-wave kernel: one problem per wave, 2 + 2 (2 + d) quantities per block
-      a.spec_ppw = 1;
-      a.spec_pg = a.G;
-      a.nq = 6 + 2 * a.d;
-    }
+    spec_setup(a, true);
   }
   a.mt = 0;
   a.mt_F = a.mt_cpb = 0;
@@ -1862,6 +1868,25 @@ int fgp_nll_partials_len(const fgp_nll_desc* desc, int64_t* len) {
     *len = std::max<int64_t>(*len, off + cnt + 1);
     *len = std::max<int64_t>(*len, 3 * (int64_t)a.G * a.nq * a.nb);   // fgp_fit_persist's three partial buffers
   }
+  return kOk;
+}
+
+int fgp_spec_geometry(const fgp_nll_desc* desc, int allow_tile, int* out) {
+  if (!desc) return set_error(kErrInvalid, "null nll desc");
+  if (!out) return set_error(kErrInvalid, "fgp_spec_geometry: null out");
+  if (!desc->basis || desc->mt_tasks) return set_error(kErrInvalid, "fgp_spec_geometry: needs the spectral desc (basis)");
+  fgp_nll_desc probe = *desc;   // no pointer is followed: placeholders for the ones a caller without a device lacks
+  static const double dummy = 0.0;
+  if (!probe.partials) probe.partials = const_cast<double*>(&dummy);
+  if (!probe.ysq) probe.ysq = &dummy;
+  if (!probe.raw) probe.raw = &dummy;
+  Nll a;
+  int rc = to_nll(&probe, a);
+  if (rc != kOk) return rc;
+  if (!allow_tile) spec_setup(a, false);
+  const int v[10] = {a.spec_tile, a.spec_ppw, a.spec_pg, a.spec_pgp, a.spec_ck, a.nb, a.spec_kpl, a.spec_ps, a.spec_nsl,
+                     a.nq};
+  for (int i = 0; i < 10; ++i) out[i] = v[i];
   return kOk;
 }
 

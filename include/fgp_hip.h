@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define FGP_ABI_VERSION 19
+#define FGP_ABI_VERSION 20
 
 #define FGP_OK 0
 #define FGP_ERR_INVALID (-1)     /* bad argument (shape, stride, null pointer) */
@@ -701,6 +701,17 @@ int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_
  * mismatch.  enable == 0 synchronises the device, disarms it and returns out[0] = group hand-offs checked,
  * out[1] = mismatches (0 when every arriver saw every stored partial). */
 int fgp_handoff_check(int enable, unsigned long long* out);
+
+/* ABI 20 -- test hook (no reference counterpart): which spectral iteration kernel a desc takes and its geometry, so a
+ * test can assert the variant it means to reach.  desc: a spectral desc (basis non-NULL, mt_tasks = 0); no pointer of it
+ * is followed and NULL ysq / raw / partials are accepted.  No HIP call is made (it works without a device); the same
+ * environment switches as a launch are read (FGP_SPEC_TILE, FGP_SPEC_SLICE_NB).  allow_tile = 0 gives the per-wave
+ * geometry (what FGP_SPEC_TILE=0 selects).  out[0..9] = { tile (1: k_spec_tile, 0: k_spec_iter / k_spec_loss_iter),
+ * ppw (problems per wave), pg (problem groups), pgp (problem groups per workgroup of the tile kernel, else 0),
+ * ck (frequencies per tile chunk, else 0), nb (k blocks = per-block partials per quantity), kpl (64-frequency chunks
+ * per block), ps (problems per slice when the tile kernel runs over problem slices, else 0), nsl (slices, 1 without),
+ * nq (quantities per problem and block: 4 + d, GCV / CV 6 + 2 d) }. */
+int fgp_spec_geometry(const fgp_nll_desc* desc, int allow_tile, int* out);
 
 /* ABI 16 -- test hook (no reference counterpart): the bound of fgp_fit_persist's in-kernel barrier polls (a
  * negative value restores the default 2^22).  0 makes every barrier wait that does not find the grid complete

@@ -126,7 +126,7 @@ def header_wide_functions():
 
 def test_abi_19_and_wide_symbols_bound():
     lib = N.lib()
-    assert lib.fgp_abi_version() == 19 and N.ABI_VERSION == 19 and N.WIDE_MAX_D == 64
+    assert lib.fgp_abi_version() == 20 and N.ABI_VERSION == 20 and N.WIDE_MAX_D == 64
     names = header_wide_functions()
     assert {"fgp_wide_lattice_points", "fgp_wide_lattice_parts", "fgp_wide_net_parts", "fgp_wide_k1", "fgp_wide_k1_bwd",
             "fgp_wide_kernel_rows", "fgp_wide_post_mean"} <= set(names)
