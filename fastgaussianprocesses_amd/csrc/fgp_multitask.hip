@@ -1050,18 +1050,6 @@ static int to_mtfit(const fgp_mt_fit_desc* d, MtFit* m, int64_t* work_bytes) {
   return kOk;
 }
 
-template <typename Fn>
-static int mtg_with_d(int d, Fn&& fn) {
-  switch (d) {
-    case 1: return fn(std::integral_constant<int, 1>{});
-    case 2: return fn(std::integral_constant<int, 2>{});
-    case 3: return fn(std::integral_constant<int, 3>{});
-    case 4: return fn(std::integral_constant<int, 4>{});
-    case 5: return fn(std::integral_constant<int, 5>{});
-    default: return fn(std::integral_constant<int, 6>{});
-  }
-}
-
 }  // namespace fgp
 
 using namespace fgp;
@@ -1181,7 +1169,7 @@ int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_
   const size_t lds = mtc_lds(m.lay, m.B);
   const bool wave_class = lds > 0 && (g_mt_class_mode == 2 || (g_mt_class_mode == 0 && (int64_t)m.G * m.lay.nmin <= kMtcMaxClasses));
   const dim3 gw((unsigned)m.lay.nmin, (unsigned)m.G);
-  return mtg_with_d(m.d, [&](auto dc) {
+  return no_kernel(dispatch_range<1, 6>(m.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     const dim3 gr((unsigned)((4 + D + m.P + kWG / 64 - 1) / (kWG / 64)), (unsigned)m.G);
     for (int it = 0; it < iters; ++it) {
@@ -1197,7 +1185,7 @@ int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_
       if (r != kOk) return r;
     }
     return (int)kOk;
-  });
+  }), "fgp_mt_fit_run", m.d);
 }
 
 }  // extern "C"

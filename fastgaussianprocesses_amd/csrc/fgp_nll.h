@@ -11,12 +11,6 @@
 
 namespace fgp {
 
-// an A/B switch of the host code: the environment variable is set and starts with '0'
-inline bool getenv_off(const char* name) {
-  const char* e = std::getenv(name);
-  return e && e[0] == '0';
-}
-
 struct Nll {
   int log2n, d, G, nb, nq;
   const double* parts;
@@ -436,32 +430,9 @@ __device__ __forceinline__ int64_t work_pos(int64_t u, int64_t k, int P1) {
 // Calls fn(std::integral_constant<int, PG>) with the parts source of `a` as a compile-time value
 // (generated lattice parts exist only for the complex / lattice instantiations).
 template <typename T, typename Fn>
-static int with_pg(const Nll& a, Fn&& fn) {
-  if constexpr (sizeof(T) == 16) {
-    switch (a.pg) {
-      case 2: return fn(std::integral_constant<int, 2>{});
-      case 4: return fn(std::integral_constant<int, 4>{});
-      case 6: return fn(std::integral_constant<int, 6>{});
-      case 8: return fn(std::integral_constant<int, 8>{});
-      default: break;
-    }
-  }
-  return fn(std::integral_constant<int, 0>{});
-}
-
-// Calls fn(std::integral_constant<int, D>{}) with d (1 .. FGP_MAX_D) as a compile-time value.
-template <typename Fn>
-static void with_d(int d, Fn&& fn) {
-  switch (d) {
-    case 1: fn(std::integral_constant<int, 1>{}); break;
-    case 2: fn(std::integral_constant<int, 2>{}); break;
-    case 3: fn(std::integral_constant<int, 3>{}); break;
-    case 4: fn(std::integral_constant<int, 4>{}); break;
-    case 5: fn(std::integral_constant<int, 5>{}); break;
-    case 6: fn(std::integral_constant<int, 6>{}); break;
-    case 7: fn(std::integral_constant<int, 7>{}); break;
-    default: fn(std::integral_constant<int, 8>{}); break;
-  }
+static int dispatch_parts(const Nll& a, Fn&& fn) {
+  if constexpr (sizeof(T) == 16) return no_kernel(dispatch_list<0, 2, 4, 6, 8>(a.pg, fn), "parts source", a.pg);
+  else return no_kernel(dispatch_list<0>(a.pg, fn), "parts source", a.pg);
 }
 
 struct Fit {
@@ -635,7 +606,7 @@ constexpr int kSpecLdsMax = FGP_SPEC_LDS_KB * 1024;   // its dynamic LDS per wor
 constexpr int kSpecScratch = 256;                  // doubles of the deferred step's totals / parameters (ring slot RING-1)
 constexpr int kSpecMaxDma = 6;                     // LDS-DMA wave-instructions per wave and chunk (tile <= 3072 doubles;
                                                    // the per-wave source pointers live in registers)
-void spec_geometry(Nll& a, bool allow_tile = true);   // nb and the spec_* fields of a spectral desc
+void spec_geometry(Nll& a, const Switches& sw, bool allow_tile = true);   // nb and the spec_* fields of a spectral desc
 int launch_spec_loss_iter(const Nll& a, hipStream_t st);   // GCV / CV partials (ABI 16)
 int launch_spec_loss_step(const Nll& a, const Fit& f, int iter, int do_update, hipStream_t st);
 int64_t spec_chunks(bool net, int log2n);          // 64-frequency chunks of the spectra (fgp_spec_basis layout)

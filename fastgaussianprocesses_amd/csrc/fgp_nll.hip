@@ -1334,8 +1334,8 @@ __global__ __launch_bounds__(kWG) void k_fwd_rows_r2c_gen(GenSpec g, int log2n, 
 // host-side launch logic
 // The spectral fields of a desc whose loss, G, d and basis_stride are set: spec_geometry, then the alternative
 // losses' per-wave kernel (one problem per wave, 2 + 2 (2 + d) quantities per block).
-static void spec_setup(Nll& a, bool allow_tile) {
-  spec_geometry(a, allow_tile && a.loss == FGP_LOSS_MLL);
+static void spec_setup(Nll& a, const Switches& sw, bool allow_tile) {
+  spec_geometry(a, sw, allow_tile && a.loss == FGP_LOSS_MLL);
   a.nq = 4 + a.d;
   if (a.loss != FGP_LOSS_MLL) {
     a.spec_ppw = 1;
@@ -1344,7 +1344,7 @@ static void spec_setup(Nll& a, bool allow_tile) {
   }
 }
 
-static int to_nll(const fgp_nll_desc* d, Nll& a) {
+static int to_nll(const fgp_nll_desc* d, Nll& a, const Switches& sw) {
   if (!d) return set_error(kErrInvalid, "null nll desc");
   if (d->family != FGP_FAMILY_LATTICE && d->family != FGP_FAMILY_NET) return set_error(kErrInvalid, "bad family");
   if (d->log2n < 4 || d->log2n > kMaxLog2N) return set_error(kErrUnsupported, "fused fit needs 4 <= log2n <= 24");
@@ -1382,16 +1382,14 @@ static int to_nll(const fgp_nll_desc* d, Nll& a) {
   a.G = d->G;
   // lattices with n >= 2^17: the real-even (RE) fit kernels when the parts are regenerated, else the
   // half-length (R2C) ones.  FGP_R2C=1 forces R2C, FGP_R2C=0 the full-length kernels.
-  const char* r2c_env = getenv("FGP_R2C");
-  const char mode = (r2c_env && r2c_env[0]) ? r2c_env[0] : '2';
-  a.r2c = d->family == FGP_FAMILY_LATTICE && d->log2n >= 17 && mode != '0';
+  a.r2c = use_r2c(sw, d->family == FGP_FAMILY_LATTICE, d->log2n);
   const int re_p2 = re_row_log2(d->log2n);
   // the real-even kernels form each mirror pair's parts from one lattice index, which needs every
   // generating vector entry odd (M z_j = n/2 mod n); an even entry takes the R2C kernels
   bool z_odd = true;
   for (int j = 0; j < d->d && d->parts_gen == FGP_PARTS_LATTICE; ++j) z_odd = z_odd && (d->gen_z[j] & 1);
   // (the real-even kernels also take n = 2^16, where the R2C ones do not run: rows of 2^11, 16 rows)
-  a.re = d->family == FGP_FAMILY_LATTICE && d->log2n >= 16 && mode != '0' && mode != '1' &&
+  a.re = d->family == FGP_FAMILY_LATTICE && d->log2n >= 16 && sw.r2c == 2 &&
          d->parts_gen == FGP_PARTS_LATTICE && re_p2 > 0 && z_odd;
   // per-block partials: one per row / row-pair workgroup (RE: N1/2 = n / 2^(P2 + 2) row pairs)
   a.nb = d->log2n > 12 ? 1 << (a.re ? d->log2n - 2 - re_p2 : d->log2n - 12 - (a.r2c ? 1 : 0)) : 1;
@@ -1442,7 +1440,7 @@ static int to_nll(const fgp_nll_desc* d, Nll& a) {
   }
   if (a.spec) {
     a.re = a.r2c = 0;
-    spec_setup(a, true);
+    spec_setup(a, sw, true);
   }
   a.mt = 0;
   a.mt_F = a.mt_cpb = 0;
@@ -1483,19 +1481,15 @@ template <typename T>
 static int launch_iter_single(const Nll& a, const Tables* tb, hipStream_t st, bool emit = false) {
   const int P = a.log2n;
   const unsigned grid = (unsigned)((a.G + (kTile >> P) - 1) / (kTile >> P));
-  return with_pg<T>(a, [&](auto pgc) {
+  return dispatch_parts<T>(a, [&](auto pgc) {
     constexpr int PG = decltype(pgc)::value;
-    switch (P) {
-#define FGP_C(PP)                                                                     \
-  case PP:                                                                            \
-    if (emit) k_iter_single<PP, T, true, PG><<<grid, kWG, 0, st>>>(a, tb->tw4096);    \
-    else k_iter_single<PP, T, false, PG><<<grid, kWG, 0, st>>>(a, tb->tw4096);        \
-    break;
-      FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-      default: return set_error(kErrInvalid, "bad log2n");
-    }
-    return check_launch("k_iter_single");
+    const int rc = dispatch_range<4, 12>(P, [&](auto pc) {
+      constexpr int PP = decltype(pc)::value;
+      if (emit) k_iter_single<PP, T, true, PG><<<grid, kWG, 0, st>>>(a, tb->tw4096);
+      else k_iter_single<PP, T, false, PG><<<grid, kWG, 0, st>>>(a, tb->tw4096);
+      return check_launch("k_iter_single");
+    });
+    return rc == kNoMatch ? set_error(kErrInvalid, "bad log2n") : rc;
   });
 }
 
@@ -1503,20 +1497,18 @@ template <typename T>
 static int launch_rows_fwd(const Nll& a, const Tables* tb, hipStream_t st) {
   const int m = a.log2n, m2 = split_m2(m);
   const unsigned grid = (unsigned)((int64_t)a.G << (m - kTileLog));
-  return with_pg<T>(a, [&](auto pgc) {
+  return dispatch_parts<T>(a, [&](auto pgc) {
     constexpr int PG = decltype(pgc)::value;
-    switch (m2) {
-#define FGP_C(PP) case PP: k_fwd_rows<PP, T, PG, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]); break;
-      FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-      case 12:   // n >= 2^16: the dimension count as a compile-time constant
-        with_d(a.d, [&](auto dc) {
-          k_fwd_rows<12, T, PG, decltype(dc)::value><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
-        });
-        break;
-      default: return set_error(kErrInvalid, "bad m2");
-    }
-    return check_launch("k_fwd_rows");
+    int rc = dispatch_range<9, 11>(m2, [&](auto pc) {
+      k_fwd_rows<decltype(pc)::value, T, PG, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+      return check_launch("k_fwd_rows");
+    });
+    if (m2 == 12)   // n >= 2^16: the dimension count as a compile-time constant
+      rc = no_kernel(dispatch_range<1, FGP_MAX_D>(a.d, [&](auto dc) {
+        k_fwd_rows<12, T, PG, decltype(dc)::value><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+        return check_launch("k_fwd_rows");
+      }), "k_fwd_rows", a.d);
+    return rc == kNoMatch ? set_error(kErrInvalid, "bad m2") : rc;
   });
 }
 
@@ -1524,37 +1516,31 @@ template <typename T>
 static int launch_cols_fwd(const Nll& a, const Tables* tb, hipStream_t st, bool emit) {
   const int m = a.log2n, m1 = m - split_m2(m);
   const unsigned grid = (unsigned)((int64_t)a.G << (m - kTileLog));
-  switch (m1) {
-#define FGP_C(PP)                                                           \
-  case PP:                                                                  \
-    if (emit) k_fwd_cols<PP, T, true><<<grid, kWG, 0, st>>>(a, tb->tw4096); \
-    else k_fwd_cols<PP, T, false><<<grid, kWG, 0, st>>>(a, tb->tw4096);     \
-    break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad m1");
-  }
-  return check_launch("k_fwd_cols");
+  const int rc = dispatch_range<4, 12>(m1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (emit) k_fwd_cols<PP, T, true><<<grid, kWG, 0, st>>>(a, tb->tw4096);
+    else k_fwd_cols<PP, T, false><<<grid, kWG, 0, st>>>(a, tb->tw4096);
+    return check_launch("k_fwd_cols");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "bad m1") : rc;
 }
 
 template <typename T>
 static int launch_rows_bwd(const Nll& a, const Tables* tb, hipStream_t st) {
   const int m = a.log2n, m2 = split_m2(m);
   const unsigned grid = (unsigned)((int64_t)a.G << (m - kTileLog));
-  return with_pg<T>(a, [&](auto pgc) {
+  return dispatch_parts<T>(a, [&](auto pgc) {
     constexpr int PG = decltype(pgc)::value;
-    switch (m2) {
-#define FGP_C(PP) case PP: k_bwd_rows<PP, T, PG, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]); break;
-      FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-      case 12:
-        with_d(a.d, [&](auto dc) {
-          k_bwd_rows<12, T, PG, decltype(dc)::value><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
-        });
-        break;
-      default: return set_error(kErrInvalid, "bad m2");
-    }
-    return check_launch("k_bwd_rows");
+    int rc = dispatch_range<9, 11>(m2, [&](auto pc) {
+      k_bwd_rows<decltype(pc)::value, T, PG, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+      return check_launch("k_bwd_rows");
+    });
+    if (m2 == 12)
+      rc = no_kernel(dispatch_range<1, FGP_MAX_D>(a.d, [&](auto dc) {
+        k_bwd_rows<12, T, PG, decltype(dc)::value><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+        return check_launch("k_bwd_rows");
+      }), "k_bwd_rows", a.d);
+    return rc == kNoMatch ? set_error(kErrInvalid, "bad m2") : rc;
   });
 }
 
@@ -1563,27 +1549,23 @@ static int launch_r2c(const Nll& a, int stage, const Tables* tb, hipStream_t st,
   const int m = a.log2n, mt = m - 1, p1 = mt - 12;
   const unsigned grid = (unsigned)((int64_t)a.G << (mt - kTileLog));
   if (stage == 0 || stage == 2) {
-    return with_pg<double2>(a, [&](auto pgc) {
+    return dispatch_parts<double2>(a, [&](auto pgc) {
       constexpr int PG = decltype(pgc)::value;
-      with_d(a.d, [&](auto dc) {
+      return no_kernel(dispatch_range<1, FGP_MAX_D>(a.d, [&](auto dc) {
         constexpr int DD = decltype(dc)::value;
         if (stage == 0) k_fwd_rows_r2c<PG, DD><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[mt]);
         else k_bwd_rows_r2c<PG, DD><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[mt]);
-      });
-      return check_launch(stage == 0 ? "k_fwd_rows_r2c" : "k_bwd_rows_r2c");
+        return check_launch(stage == 0 ? "k_fwd_rows_r2c" : "k_bwd_rows_r2c");
+      }), "k_rows_r2c", a.d);
     });
   }
-  switch (p1) {
-#define FGP_C(PP)                                                                              \
-  case PP:                                                                                     \
-    if (emit) k_fwd_cols_r2c<PP, 1><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);       \
-    else k_fwd_cols_r2c<PP, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);           \
-    break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad r2c m1");
-  }
-  return check_launch("k_fwd_cols_r2c");
+  const int rc = dispatch_range<4, 11>(p1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (emit) k_fwd_cols_r2c<PP, 1><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+    else k_fwd_cols_r2c<PP, 0><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[m]);
+    return check_launch("k_fwd_cols_r2c");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "bad r2c m1") : rc;
 }
 
 // one kernel of the pipeline: 0 = forward rows (n <= 4096: the single-kernel iteration), 1 = eigen
@@ -1658,11 +1640,12 @@ static int check_per_problem(const Nll& a, const Fit& f) {
   return kOk;
 }
 
-static int fit_step(const Nll& a, const Fit& f, int iter, int do_update, hipStream_t st, bool counter_zero = false) {
+static int fit_step(const Nll& a, const Fit& f, const Switches& sw, int iter, int do_update, hipStream_t st,
+                    bool counter_zero = false) {
   if (a.mt && a.mt_learn) return launch_mt_learn_step(a, f, iter, do_update, st);
   if (a.spec && a.loss != FGP_LOSS_MLL) return launch_spec_loss_step(a, f, iter, do_update, st);
   if (f.per_problem && a.spec) return launch_spec_reduce_step(a, f, iter, do_update, st);
-  if (a.spec && a.nb <= kSpecBlocks && !getenv_off("FGP_SPEC_STEP_MANY")) {
+  if (a.spec && a.nb <= kSpecBlocks && sw.spec_step_many) {
     // one loss over many problems: the parallel step (k_spec_step_many); its counter is zeroed once per run
     if (!counter_zero && hipMemsetAsync(spec_step_many_counter(a), 0, sizeof(unsigned), st) != hipSuccess)
       return set_error(kErrHip, "fit step: counter reset failed");
@@ -1789,14 +1772,14 @@ int fgp_spec_basis_gen(const int64_t* z, int log2n, int d, int order, const doub
 
 int fgp_nll_fwd(const fgp_nll_desc* desc, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   return nll_fwd(a, (hipStream_t)stream, desc->family == FGP_FAMILY_LATTICE);
 }
 
 int fgp_spec_inv_eig(const fgp_nll_desc* desc, double* wa, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   if (!a.spec || a.mt) return set_error(kErrInvalid, "fgp_spec_inv_eig: needs the spectral desc (basis)");
   if (!wa) return set_error(kErrInvalid, "fgp_spec_inv_eig: null wa");
@@ -1806,7 +1789,7 @@ int fgp_spec_inv_eig(const fgp_nll_desc* desc, double* wa, void* stream) {
 int fgp_spec_post_var(const fgp_nll_desc* desc, const void* psi, int64_t N, const double* part0, double* out,
                       double* partial, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   if (!a.spec || a.mt || a.spec_net || a.basis_stride != 0 || a.d > 4)
     return set_error(kErrInvalid, "fgp_spec_post_var: needs the lattice spectral desc with shared spectra, d <= 4");
@@ -1821,7 +1804,7 @@ int fgp_spec_post_var(const fgp_nll_desc* desc, const void* psi, int64_t N, cons
 
 int fgp_nll_lam(const fgp_nll_desc* desc, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   if (!desc->grad_lam) return set_error(kErrInvalid, "fgp_nll_lam: null grad_lam (the output)");
   if (a.mt) return set_error(kErrUnsupported, "fgp_nll_lam: not available for the multitask spectral fit");
@@ -1855,7 +1838,7 @@ int fgp_nll_partials_len(const fgp_nll_desc* desc, int64_t* len) {
   if (!probe.ysq) probe.ysq = &dummy;
   if (!probe.raw) probe.raw = &dummy;
   Nll a;
-  int rc = to_nll(&probe, a);
+  int rc = to_nll(&probe, a, read_switches());
   if (rc != kOk) return rc;
   if (!len) return set_error(kErrInvalid, "fgp_nll_partials_len: null len");
   const int64_t nb_doc = std::max<int64_t>(1, ((int64_t)1 << a.log2n) >> 12);
@@ -1881,9 +1864,10 @@ int fgp_spec_geometry(const fgp_nll_desc* desc, int allow_tile, int* out) {
   if (!probe.ysq) probe.ysq = &dummy;
   if (!probe.raw) probe.raw = &dummy;
   Nll a;
-  int rc = to_nll(&probe, a);
+  const Switches sw = read_switches();
+  int rc = to_nll(&probe, a, sw);
   if (rc != kOk) return rc;
-  if (!allow_tile) spec_setup(a, false);
+  if (!allow_tile) spec_setup(a, sw, false);
   const int v[10] = {a.spec_tile, a.spec_ppw, a.spec_pg, a.spec_pgp, a.spec_ck, a.nb, a.spec_kpl, a.spec_ps, a.spec_nsl,
                      a.nq};
   for (int i = 0; i < 10; ++i) out[i] = v[i];
@@ -1892,14 +1876,14 @@ int fgp_spec_geometry(const fgp_nll_desc* desc, int allow_tile, int* out) {
 
 int fgp_nll_stage(const fgp_nll_desc* desc, int stage, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   return nll_stage(a, stage, (hipStream_t)stream, desc->family == FGP_FAMILY_LATTICE);
 }
 
 int fgp_nll_bwd(const fgp_nll_desc* desc, void* stream) {
   Nll a;
-  int rc = to_nll(desc, a);
+  int rc = to_nll(desc, a, read_switches());
   if (rc != kOk) return rc;
   return nll_bwd(a, (hipStream_t)stream, desc->family == FGP_FAMILY_LATTICE);
 }
@@ -1958,17 +1942,13 @@ static int fftbr_real_any(const T* in, int64_t in_batch_stride, void* out, int64
   a.grad_lam = out;
   a.out_stride = out_stride;
   a.stamps = nullptr;
-  switch (p1) {
-#define FGP_C(PP)                                                                                   \
-  case PP:                                                                                          \
-    if (half) k_fwd_cols_r2c<PP, 3><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]);           \
-    else k_fwd_cols_r2c<PP, 1><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]);                \
-    break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad r2c m1");
-  }
-  return check_launch("k_fwd_cols_r2c");
+  rc = dispatch_range<4, 11>(p1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (half) k_fwd_cols_r2c<PP, 3><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]);
+    else k_fwd_cols_r2c<PP, 1><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]);
+    return check_launch("k_fwd_cols_r2c");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "bad r2c m1") : rc;
 }
 }  // extern "C++"
 
@@ -1991,20 +1971,15 @@ static int ifftbr_real_any(const void* in, int64_t in_batch_stride, const void* 
   const unsigned grid = (unsigned)(batch * tiles);
   const double2* X = static_cast<const double2*>(in);
   double2* wk = static_cast<double2*>(work);
-  switch (p1) {
-#define FGP_C(PP)                                                                                                \
-  case PP:                                                                                                       \
-    if (freal) k_inv_cols_c2r<PP, true, true><<<grid, kWG, 0, st>>>(X, in_batch_stride, f, f_batch_stride, wk,  \
-                                                                    log2n, tb->tw4096, tb->twm[log2n]);          \
-    else k_inv_cols_c2r<PP, false, false><<<grid, kWG, 0, st>>>(X, in_batch_stride, f, f_batch_stride, wk,      \
-                                                                log2n, tb->tw4096, tb->twm[log2n]);              \
-    break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad c2r m1");
-  }
-  int rc = check_launch("k_inv_cols_c2r");
-  if (rc != kOk) return rc;
+  const int rc = dispatch_range<4, 11>(p1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (freal) k_inv_cols_c2r<PP, true, true><<<grid, kWG, 0, st>>>(X, in_batch_stride, f, f_batch_stride, wk, log2n,
+                                                                    tb->tw4096, tb->twm[log2n]);
+    else k_inv_cols_c2r<PP, false, false><<<grid, kWG, 0, st>>>(X, in_batch_stride, f, f_batch_stride, wk, log2n,
+                                                                tb->tw4096, tb->twm[log2n]);
+    return check_launch("k_inv_cols_c2r");
+  });
+  if (rc != kOk) return rc == kNoMatch ? set_error(kErrInvalid, "bad c2r m1") : rc;
   k_inv_rows_c2r<<<grid, kWG, 0, st>>>(wk, log2n, out, out_batch_stride, tb->tw4096, tb->twm[mt]);
   return check_launch("k_inv_rows_c2r");
 }
@@ -2040,30 +2015,22 @@ int spec_basis_r2c(const double* parts, int d, int log2n, int s0, int cnt, doubl
     return set_error(kErrHip, "spec_basis_r2c: memset failed");
   const unsigned grid = (unsigned)(tiles * cnt);
   double2* wk = static_cast<double2*>(work);
+  int rc;
   if (gen) {
-    auto go = [&](auto oc) {
-      constexpr int O = decltype(oc)::value;
-      switch (d) {
-#define FGP_R(DD) case DD: k_fwd_rows_r2c_gen<DD, O><<<grid, kWG, 0, st>>>(*gen, log2n, s0, cnt, wk, tb->tw4096, tb->twm[mt]); break;
-        FGP_R(1) FGP_R(2) FGP_R(3) FGP_R(4) FGP_R(5) FGP_R(6)
-#undef FGP_R
-      }
-    };
-    switch (gen->order) {
-      case 2: go(std::integral_constant<int, 2>{}); break;
-      case 4: go(std::integral_constant<int, 4>{}); break;
-      case 6: go(std::integral_constant<int, 6>{}); break;
-      case 8: go(std::integral_constant<int, 8>{}); break;
-      default: return set_error(kErrUnsupported, "Bernoulli order %d unsupported", gen->order);
-    }
+    rc = dispatch_list<2, 4, 6, 8>(gen->order, [&](auto oc) {
+      return no_kernel(dispatch_range<1, kSpecMaxD>(d, [&](auto dc) {
+        k_fwd_rows_r2c_gen<decltype(dc)::value, decltype(oc)::value><<<grid, kWG, 0, st>>>(*gen, log2n, s0, cnt, wk,
+                                                                                          tb->tw4096, tb->twm[mt]);
+        return check_launch("k_fwd_rows_r2c_gen");
+      }), "k_fwd_rows_r2c_gen", d);
+    });
+    if (rc == kNoMatch) return set_error(kErrUnsupported, "Bernoulli order %d unsupported", gen->order);
   } else {
-    switch (d) {
-#define FGP_R(DD) case DD: k_fwd_rows_r2c_prod<DD><<<grid, kWG, 0, st>>>(parts, log2n, s0, cnt, wk, tb->tw4096, tb->twm[mt]); break;
-      FGP_R(1) FGP_R(2) FGP_R(3) FGP_R(4) FGP_R(5) FGP_R(6)
-#undef FGP_R
-    }
+    rc = no_kernel(dispatch_range<1, kSpecMaxD>(d, [&](auto dc) {
+      k_fwd_rows_r2c_prod<decltype(dc)::value><<<grid, kWG, 0, st>>>(parts, log2n, s0, cnt, wk, tb->tw4096, tb->twm[mt]);
+      return check_launch("k_fwd_rows_r2c_prod");
+    }), "k_fwd_rows_r2c_prod", d);
   }
-  int rc = check_launch(gen ? "k_fwd_rows_r2c_gen" : "k_fwd_rows_r2c_prod");
   if (rc != kOk) return rc;
   Nll a{};
   a.log2n = log2n;
@@ -2072,13 +2039,11 @@ int spec_basis_r2c(const double* parts, int d, int log2n, int s0, int cnt, doubl
   a.work = work;
   a.grad_lam = basis + 64 * (int64_t)s0;
   a.stamps = nullptr;
-  switch (p1) {
-#define FGP_C(PP) case PP: k_fwd_cols_r2c<PP, 2><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]); break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad r2c m1");
-  }
-  return check_launch("k_fwd_cols_r2c");
+  rc = dispatch_range<4, 11>(p1, [&](auto pc) {
+    k_fwd_cols_r2c<decltype(pc)::value, 2><<<grid, kWG, 0, st>>>(a, tb->tw4096, tb->twm[log2n]);
+    return check_launch("k_fwd_cols_r2c");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "bad r2c m1") : rc;
 }
 
 // fgp_handoff_check's device buffer while armed (kHandoffWords XOR words, checks, mismatches)
@@ -2091,11 +2056,12 @@ extern "C" {
 int fgp_fit_step(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter, int do_update, void* stream) {
   Nll a;
   Fit f;
-  int rc = to_nll(nll, a);
+  const Switches sw = read_switches();
+  int rc = to_nll(nll, a, sw);
   if (rc == kOk) rc = to_fit(fit, f);
   if (rc == kOk) rc = check_per_problem(a, f);
   if (rc != kOk) return rc;
-  return fit_step(a, f, iter, do_update, (hipStream_t)stream);
+  return fit_step(a, f, sw, iter, do_update, (hipStream_t)stream);
 }
 
 int fgp_fit_persist_ok(const fgp_nll_desc* nll, int* ok) {
@@ -2107,7 +2073,7 @@ int fgp_fit_persist_ok(const fgp_nll_desc* nll, int* ok) {
   if (!probe.ysq) probe.ysq = &dummy;
   if (!probe.raw) probe.raw = &dummy;
   Nll a;
-  int rc = to_nll(&probe, a);
+  int rc = to_nll(&probe, a, read_switches());
   if (rc != kOk) return rc;
   int W, bpw;
   size_t shm;
@@ -2119,7 +2085,7 @@ int fgp_fit_persist(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iters,
                     void* stream) {
   Nll a;
   Fit f;
-  int rc = to_nll(nll, a);
+  int rc = to_nll(nll, a, read_switches());
   if (rc == kOk) rc = to_fit(fit, f);
   if (rc != kOk) return rc;
   if (!ctrl) return set_error(kErrInvalid, "fgp_fit_persist: null ctrl");
@@ -2163,10 +2129,10 @@ int fgp_handoff_check(int enable, unsigned long long* out) {
 }  // extern "C"
 
 static int fit_run_enqueue(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter0, int iters, int final_no_update,
-                           void* stream) {
+                           const Switches& sw, void* stream) {
   Nll a;
   Fit f;
-  int rc = to_nll(nll, a);
+  int rc = to_nll(nll, a, sw);
   if (rc == kOk) rc = to_fit(fit, f);
   if (rc == kOk) rc = check_per_problem(a, f);
   if (rc != kOk) return rc;
@@ -2197,8 +2163,7 @@ static int fit_run_enqueue(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int
       return set_error(kErrHip, "fgp_fit_run: counter reset failed");
     if (fuse_spec) fz.check = g_handoff_check;
   }
-  const char* pe = getenv("FGP_SPEC_PERSIST");   // (opt-in until measured on the device: FGP_SPEC_PERSIST=1)
-  if (fuse_spec && pe && pe[0] == '1' && spec_nparams(a) <= kSpecStateMax) {
+  if (fuse_spec && sw.spec_persist && spec_nparams(a) <= kSpecStateMax) {
     // every iteration and the last step in ONE persistent k_spec_tile launch (falls through to the launch
     // per iteration when the grid cannot be co-resident)
     fz.iter = iter0;
@@ -2231,7 +2196,7 @@ static int fit_run_enqueue(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int
     }
     return kOk;
   }
-  const bool many = a.spec && !f.per_problem && a.nb <= kSpecBlocks && !getenv_off("FGP_SPEC_STEP_MANY");
+  const bool many = a.spec && !f.per_problem && a.nb <= kSpecBlocks && sw.spec_step_many;
   if (many && iters > 0 && hipMemsetAsync(spec_step_many_counter(a), 0, sizeof(unsigned), st) != hipSuccess)
     return set_error(kErrHip, "fgp_fit_run: counter reset failed");
   for (int it = 0; it < iters; ++it) {
@@ -2244,7 +2209,7 @@ static int fit_run_enqueue(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int
       continue;
     }
     if ((rc = nll_bwd(a, st, lat)) != kOk) return rc;
-    if ((rc = fit_step(a, f, iter0 + it, upd, st, many)) != kOk) return rc;
+    if ((rc = fit_step(a, f, sw, iter0 + it, upd, st, many)) != kOk) return rc;
   }
   return kOk;
 }
@@ -2314,16 +2279,17 @@ extern "C" {
 
 int fgp_fit_run(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter0, int iters, int final_no_update,
                 void* stream) {
-  return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, stream);
+  return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, read_switches(), stream);
 }
 
 int fgp_fit_run_graph(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter0, int iters, int final_no_update,
                       long long token, void* stream) {
   hipStream_t st = (hipStream_t)stream;
+  const Switches sw = read_switches();
   if (!nll || !fit || !fit_graph_wanted(nll, st)) {
     std::lock_guard<std::mutex> lock(g_fg_mu);
     ++g_fg_stats[2];
-    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, stream);
+    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, sw, stream);
   }
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64)
@@ -2336,13 +2302,9 @@ int fgp_fit_run_graph(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter
   key_put(key, ints, sizeof(ints));
   const void* hook = g_handoff_check;
   key_put(key, &hook, sizeof(hook));
-  // the library's A/B switches that choose kernels / workspace layouts for a desc are inputs of the sequence too
-  for (const char* nm : {"FGP_SPEC_TILE", "FGP_SPEC_SLICE_NB", "FGP_SPEC_PERSIST", "FGP_SPEC_STEP_MANY", "FGP_R2C"}) {
-    const char* v = getenv(nm);
-    key_put(key, nm, strlen(nm));
-    if (v) key_put(key, v, strlen(v) + 1);
-    else key.push_back(0xff);
-  }
+  // the library's A/B switches that choose kernels / workspace layouts for a desc are inputs of the sequence too:
+  // the very struct the launch code below reads
+  key_put(key, &sw, sizeof(sw));
   std::lock_guard<std::mutex> lock(g_fg_mu);
   for (auto& e : g_fit_graphs)
     if (e.token == token && e.dev == dev && e.key == key) {
@@ -2357,9 +2319,9 @@ int fgp_fit_run_graph(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter
   if (hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal) != hipSuccess) {
     (void)hipGetLastError();
     ++g_fg_stats[2];
-    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, stream);
+    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, sw, stream);
   }
-  const int rc = fit_run_enqueue(nll, fit, iter0, iters, final_no_update, cap);
+  const int rc = fit_run_enqueue(nll, fit, iter0, iters, final_no_update, sw, cap);
   hipGraph_t g = nullptr;
   const hipError_t ec = hipStreamEndCapture(cap, &g);
   hipGraphExec_t exec = nullptr;
@@ -2371,7 +2333,7 @@ int fgp_fit_run_graph(const fgp_nll_desc* nll, const fgp_fit_desc* fit, int iter
     (void)hipGetLastError();
     if (rc != kOk) return rc;                       // an argument error: reported as the eager call would
     ++g_fg_stats[2];
-    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, stream);
+    return fit_run_enqueue(nll, fit, iter0, iters, final_no_update, sw, stream);
   }
   ++g_fg_stats[1];
   FitGraph* slot = nullptr;

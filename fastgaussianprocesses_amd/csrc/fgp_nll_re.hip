@@ -608,38 +608,36 @@ static int launch_re_p2(const Nll& a, int stage, const Tables* tb, hipStream_t s
   const double2* tw2 = P2 >= 12 ? tb->twm[13] : tb->tw4096;
   if (stage == 0 || stage == 2) {
     const unsigned grid = (unsigned)((int64_t)a.G << (p1 - 1));
-    return with_pg<double2>(a, [&](auto pgc) {
+    return dispatch_parts<double2>(a, [&](auto pgc) {
       constexpr int PG = decltype(pgc)::value;
       if constexpr (PG == 0) {
         return set_error(kErrInvalid, "real-even fit kernels need the lattice parts generator");
       } else {
-        with_d(a.d, [&](auto dc) {
+        return no_kernel(dispatch_range<1, FGP_MAX_D>(a.d, [&](auto dc) {
           constexpr int DD = decltype(dc)::value;
           if (stage == 0)
             k_fwd_rows_re<P2, PG, DD><<<grid, Geo::WG, 0, st>>>(a, tb->tw4096, tb->twm[mt], tb->twm[m], tw2);
           else
             k_bwd_rows_re<P2, PG, DD><<<grid, Geo::WG, 0, st>>>(a, tb->tw4096, tb->twm[mt], tb->twm[m], tw2, fz);
-        });
-        return check_launch(stage == 0 ? "k_fwd_rows_re" : "k_bwd_rows_re");
+          return check_launch(stage == 0 ? "k_fwd_rows_re" : "k_bwd_rows_re");
+        }), "k_rows_re", a.d);
       }
     });
   }
   if (stage != 1) return set_error(kErrInvalid, "bad stage %d", stage);
   const unsigned grid = (unsigned)((int64_t)a.G << (m - 14));
-  switch (p1) {
-#define FGP_C(PP) case PP: k_fwd_cols_re<P2, PP><<<grid, kWG, 0, st>>>(a, tb->tw4096); break;
-    FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "bad re m1");
-  }
-  return check_launch("k_fwd_cols_re");
+  const int rc = dispatch_range<4, 12>(p1, [&](auto pc) {
+    k_fwd_cols_re<P2, decltype(pc)::value><<<grid, kWG, 0, st>>>(a, tb->tw4096);
+    return check_launch("k_fwd_cols_re");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "bad re m1") : rc;
 }
 
 static int launch_re_any(const Nll& a, int stage, const Tables* tb, hipStream_t st, const FitFuse& fz) {
-  switch (re_row_log2(a.log2n)) {
-    case 11: return launch_re_p2<11>(a, stage, tb, st, fz);
-    default: return set_error(kErrInvalid, "real-even fit kernels: no row split for log2n=%d", a.log2n);
-  }
+  const int rc = dispatch_list<11>(re_row_log2(a.log2n), [&](auto pc) {
+    return launch_re_p2<decltype(pc)::value>(a, stage, tb, st, fz);
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "real-even fit kernels: no row split for log2n=%d", a.log2n) : rc;
 }
 
 int launch_re(const Nll& a, int stage, const Tables* tb, hipStream_t st) {

@@ -703,30 +703,6 @@ static const void* post_mean_kernel(bool uniform4, int B) {
                                 : reinterpret_cast<const void*>(k_post_mean<FAM, D, kPmB, 0>);
 }
 
-// Workgroups of a post_mean instance resident at once on the current device (workgroups per CU x CUs), queried
-// once per instance and remembered (no query inside a hipGraph capture after the first eager call); 0 if unknown.
-static int64_t post_mean_resident(const void* kp) {
-  // keyed by (instance, device): devices of one process may differ in CU count / partition mode
-  static const void* rk[256];
-  static int rdev[256];
-  static int64_t rres[256];
-  static int nr = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  for (int i = 0; i < nr; ++i)
-    if (rk[i] == kp && rdev[i] == dev) return rres[i];
-  int per_cu = 0, cus = 0;
-  const int64_t res = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, kWG, 0) == hipSuccess)
-                          ? (int64_t)per_cu * cus : 0;
-  if (nr < 256) {
-    rk[nr] = kp;
-    rdev[nr] = dev;
-    rres[nr++] = res;
-  }
-  return res;
-}
-
 // Training points per workgroup of a batched launch: the workgroups of an FP64-VALU-bound launch run in rounds of
 // `resident`; with W workgroups the last round is W / resident - floor(W / resident) full, so of the chunks
 // {2048, 1024, 512} (whole 256-point slabs; a workgroup's prologue ~1 % of a 512-point chunk) the one whose launch
@@ -737,13 +713,11 @@ static int64_t post_mean_chunk(int d, const PredSpec& spec, int64_t n, int64_t N
   bool uniform4 = true;
   for (int j = 0; j < d; ++j) uniform4 = uniform4 && spec.order[j] == 4;
   const void* kp = nullptr;
-  switch (d) {
-#define FGP_C(DD) case DD: kp = post_mean_kernel<FAM, DD>(uniform4, B); break;
-    FGP_C(1) FGP_C(2) FGP_C(3) FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8)
-#undef FGP_C
-    default: return kChunk;
-  }
-  const int64_t res = post_mean_resident(kp);
+  (void)dispatch_range<1, FGP_MAX_D>(d, [&](auto dc) {
+    kp = post_mean_kernel<FAM, decltype(dc)::value>(uniform4, B);
+    return kOk;
+  });
+  const int64_t res = kp ? resident_workgroups(kp, kWG, 0, 0) : 0;
   if (res <= 0) return kChunk;
   const int64_t tiles = (N + kWG - 1) / kWG;
   int64_t best = kChunk;
@@ -769,15 +743,12 @@ static int launch_post_mean(int d, const double* xt, int64_t N, const void* z, i
   const dim3 grid((unsigned)nchunks, (unsigned)((N + kWG - 1) / kWG), (unsigned)P);
   bool uniform4 = true;
   for (int j = 0; j < d; ++j) uniform4 = uniform4 && spec.order[j] == 4;
-  switch (d) {
-#define FGP_C(DD) \
-  case DD: post_mean_d<FAM, DD>(grid, st, uniform4, B, xt, N, z, n, spec, tbits, hyp, Gk, coeffs, cstride, work, nchunks, ps, chunk); break;
-    FGP_C(1) FGP_C(2) FGP_C(3) FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8)
-#undef FGP_C
-    default: return set_error(kErrUnsupported, "post_mean: d=%d unsupported", d);
-  }
-  int rc = check_launch("k_post_mean");
-  if (rc != kOk) return rc;
+  const int rc = dispatch_range<1, FGP_MAX_D>(d, [&](auto dc) {
+    post_mean_d<FAM, decltype(dc)::value>(grid, st, uniform4, B, xt, N, z, n, spec, tbits, hyp, Gk, coeffs, cstride, work,
+                                          nchunks, ps, chunk);
+    return check_launch("k_post_mean");
+  });
+  if (rc != kOk) return rc == kNoMatch ? set_error(kErrUnsupported, "post_mean: d=%d unsupported", d) : rc;
   k_sum_chunks<<<(unsigned)((int64_t)P * B * N), kWG, 0, st>>>(work, nchunks, out, out_stride, N);
   return check_launch("k_sum_chunks");
 }
@@ -786,13 +757,11 @@ template <int FAM>
 static int launch_rows(int d, const double* xt, int64_t N, const void* z, int64_t n, const PredSpec& spec, int tbits,
                        const double* hyp, int Gk, double* rows, hipStream_t st) {
   const dim3 grid((unsigned)((n + kWG - 1) / kWG), (unsigned)N);
-  switch (d) {
-#define FGP_C(DD) case DD: k_kernel_rows<FAM, DD><<<grid, kWG, 0, st>>>(xt, N, z, n, spec, tbits, hyp, Gk, rows); break;
-    FGP_C(1) FGP_C(2) FGP_C(3) FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8)
-#undef FGP_C
-    default: return set_error(kErrUnsupported, "kernel_rows: d=%d unsupported", d);
-  }
-  return check_launch("k_kernel_rows");
+  const int rc = dispatch_range<1, FGP_MAX_D>(d, [&](auto dc) {
+    k_kernel_rows<FAM, decltype(dc)::value><<<grid, kWG, 0, st>>>(xt, N, z, n, spec, tbits, hyp, Gk, rows);
+    return check_launch("k_kernel_rows");
+  });
+  return rc == kNoMatch ? set_error(kErrUnsupported, "kernel_rows: d=%d unsupported", d) : rc;
 }
 
 // Lattice: Bernoulli order 2 alpha and coefficient per dimension.  Net: Walsh order alpha per dimension
@@ -869,16 +838,14 @@ int fgp_post_mean(int family, const double* xt, int64_t N, const void* z, int64_
 
 namespace fgp {
 // partials per (problem, test point) written by launch_qf: one per column tile of the transform
-static int64_t qf_partials(int family, int log2n) {
-  const char* r2c_env = getenv("FGP_R2C");
-  const bool r2c = family == FGP_FAMILY_LATTICE && log2n >= 17 && !(r2c_env && r2c_env[0] == '0');
-  return (int64_t)1 << (log2n - kTileLog - (r2c ? 1 : 0));
+static int64_t qf_partials(const Switches& sw, int family, int log2n) {
+  return (int64_t)1 << (log2n - kTileLog - (use_r2c(sw, family == FGP_FAMILY_LATTICE, log2n) ? 1 : 0));
 }
 
 // quadratic-form partials of P problems x N test points (k_qf_rows + k_qf_cols)
-static int launch_qf(int family, const double* xt, int64_t N, const void* z, int log2n, int d, int tbits,
-                     const PredSpec& spec, const double* hyp, const double* wa, void* work, double* partial, int64_t P,
-                     const ProbStrides& ps, hipStream_t st, const fgp_pred_desc* gdesc = nullptr) {
+static int launch_qf(const Switches& sw, int family, const double* xt, int64_t N, const void* z, int log2n, int d,
+                     int tbits, const PredSpec& spec, const double* hyp, const double* wa, void* work, double* partial,
+                     int64_t P, const ProbStrides& ps, hipStream_t st, const fgp_pred_desc* gdesc = nullptr) {
   const Tables* tb = get_tables(st);
   if (!tb) return set_error(kErrHip, "twiddle table initialisation failed");
   QfArgs q;
@@ -912,64 +879,43 @@ static int launch_qf(int family, const double* xt, int64_t N, const void* z, int
     q.gss = gdesc->gen_shift_stride;
   }
   int rc;
-  const char* r2c_env = getenv("FGP_R2C");
-  if (family == FGP_FAMILY_LATTICE && log2n >= 17 && !(r2c_env && r2c_env[0] == '0')) {
+  if (use_r2c(sw, family == FGP_FAMILY_LATTICE, log2n)) {
     // half-length (R2C) quadratic form: (P N) x (n/2 / 4096) workgroups per pass
     const int mt = log2n - 1, p1 = mt - 12;
     const dim3 grid((unsigned)((P * N) << (mt - kTileLog)));
     bool uniform4 = true;
     for (int j = 0; j < d; ++j) uniform4 = uniform4 && spec.order[j] == 4;
-    switch (d) {
-#define FGP_C(DD)                                                                          \
-  case DD:                                                                                 \
-    if (uniform4) k_qf_rows_r2c<DD, 4><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[mt]);  \
-    else k_qf_rows_r2c<DD, 0><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[mt]);           \
-    break;
-      FGP_C(1) FGP_C(2) FGP_C(3) FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8)
-#undef FGP_C
-      default: return set_error(kErrUnsupported, "post_var: d=%d unsupported", d);
-    }
-    if ((rc = check_launch("k_qf_rows_r2c")) != kOk) return rc;
-    switch (p1) {
-#define FGP_C(PP) case PP: k_qf_cols_r2c<PP><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[log2n]); break;
-      FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11)
-#undef FGP_C
-      default: return set_error(kErrInvalid, "bad r2c m1");
-    }
-    return check_launch("k_qf_cols_r2c");
+    rc = dispatch_range<1, FGP_MAX_D>(d, [&](auto dc) {
+      constexpr int DD = decltype(dc)::value;
+      if (uniform4) k_qf_rows_r2c<DD, 4><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[mt]);
+      else k_qf_rows_r2c<DD, 0><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[mt]);
+      return check_launch("k_qf_rows_r2c");
+    });
+    if (rc != kOk) return rc == kNoMatch ? set_error(kErrUnsupported, "post_var: d=%d unsupported", d) : rc;
+    rc = dispatch_range<4, 11>(p1, [&](auto pc) {
+      k_qf_cols_r2c<decltype(pc)::value><<<grid, kWG, 0, st>>>(q, tb->tw4096, tb->twm[log2n]);
+      return check_launch("k_qf_cols_r2c");
+    });
+    return rc == kNoMatch ? set_error(kErrInvalid, "bad r2c m1") : rc;
   }
   const int m2 = split_m2(log2n), m1 = log2n - m2;
   const dim3 grid((unsigned)((P * N) << (log2n - kTileLog)));
   const double2* tw = tb->tw4096;
   const double2* twm = tb->twm[log2n];
-  if (family == FGP_FAMILY_LATTICE) {
-    switch (m2) {
-#define FGP_C(PP) case PP: k_qf_rows<PP, double2><<<grid, kWG, 0, st>>>(q, tw, twm); break;
-      FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    }
-  } else {
-    switch (m2) {
-#define FGP_C(PP) case PP: k_qf_rows<PP, double><<<grid, kWG, 0, st>>>(q, tw, twm); break;
-      FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    }
-  }
-  if ((rc = check_launch("k_qf_rows")) != kOk) return rc;
-  if (family == FGP_FAMILY_LATTICE) {
-    switch (m1) {
-#define FGP_C(PP) case PP: k_qf_cols<PP, double2><<<grid, kWG, 0, st>>>(q, tw); break;
-      FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    }
-  } else {
-    switch (m1) {
-#define FGP_C(PP) case PP: k_qf_cols<PP, double><<<grid, kWG, 0, st>>>(q, tw); break;
-      FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8) FGP_C(9) FGP_C(10) FGP_C(11) FGP_C(12)
-#undef FGP_C
-    }
-  }
-  return check_launch("k_qf_cols");
+  const bool lat = family == FGP_FAMILY_LATTICE;
+  rc = no_kernel(dispatch_range<9, 12>(m2, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (lat) k_qf_rows<PP, double2><<<grid, kWG, 0, st>>>(q, tw, twm);
+    else k_qf_rows<PP, double><<<grid, kWG, 0, st>>>(q, tw, twm);
+    return check_launch("k_qf_rows");
+  }), "k_qf_rows", m2);
+  if (rc != kOk) return rc;
+  return no_kernel(dispatch_range<4, 12>(m1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (lat) k_qf_cols<PP, double2><<<grid, kWG, 0, st>>>(q, tw);
+    else k_qf_cols<PP, double><<<grid, kWG, 0, st>>>(q, tw);
+    return check_launch("k_qf_cols");
+  }), "k_qf_cols", m1);
 }
 }  // namespace fgp
 
@@ -987,9 +933,10 @@ int fgp_post_var_qf(int family, const double* xt, int64_t N, const void* z, int 
   int rc = make_spec(family, d, order, coef, spec);
   if (rc != kOk) return rc;
   hipStream_t st = (hipStream_t)stream;
-  rc = launch_qf(family, xt, N, z, log2n, d, tbits, spec, hyp, wa, work, partial, 1, ProbStrides{0, 0, 0, 0}, st);
+  const Switches sw = read_switches();
+  rc = launch_qf(sw, family, xt, N, z, log2n, d, tbits, spec, hyp, wa, work, partial, 1, ProbStrides{0, 0, 0, 0}, st);
   if (rc != kOk) return rc;
-  k_sum_chunks<<<(unsigned)N, kWG, 0, st>>>(partial, qf_partials(family, log2n), out, N, N);
+  k_sum_chunks<<<(unsigned)N, kWG, 0, st>>>(partial, qf_partials(sw, family, log2n), out, N, N);
   return check_launch("k_sum_chunks");
 }
 
@@ -1053,10 +1000,11 @@ int fgp_post_var_batched(const fgp_pred_desc* pd, const double* xt, int64_t xt_s
     p0.coef[j] = j < d ? part0[j] : 0.0;
   }
   hipStream_t st = (hipStream_t)stream;
-  rc = launch_qf(pd->family, xt, N, pd->z, log2n, d, pd->tbits, spec, pd->hyp, pd->wa, work, partial, pd->P,
+  const Switches sw = read_switches();
+  rc = launch_qf(sw, pd->family, xt, N, pd->z, log2n, d, pd->tbits, spec, pd->hyp, pd->wa, work, partial, pd->P,
                  ProbStrides{xt_stride, pd->z_stride, pd->hyp_stride, pd->wa_stride}, st, pd);
   if (rc != kOk) return rc;
-  k_qf_finish<<<(unsigned)((int64_t)pd->P * N), kWG, 0, st>>>(partial, qf_partials(pd->family, log2n), pd->hyp,
+  k_qf_finish<<<(unsigned)((int64_t)pd->P * N), kWG, 0, st>>>(partial, qf_partials(sw, pd->family, log2n), pd->hyp,
                                                                pd->hyp_stride, p0, d, N, out);
   return check_launch("k_qf_finish");
 }

@@ -1,8 +1,12 @@
-// Error reporting + per-device twiddle tables for the fgp C-ABI.
+// Error reporting, per-device twiddle tables, kernel residency and the environment switches for the fgp C-ABI.
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <mutex>
+#include <vector>
 
 #include "fgp_common.h"
 #include "fgp_runtime.h"
@@ -24,6 +28,67 @@ int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return set_error(kErrHip, "%s: %s", what, hipGetErrorString(e));
   return kOk;
+}
+
+int no_kernel(int rc, const char* what, int v) {
+  return rc == kNoMatch ? set_error(kErrInvalid, "%s: no kernel for %d", what, v) : rc;
+}
+
+namespace {
+struct Resident {
+  int dev;
+  const void* kernel;
+  size_t lds;        // (raised limits: unused)
+  int64_t wgs;
+};
+std::mutex g_res_mu;
+std::vector<Resident> g_resident, g_raised;
+
+void raise_locked(int dev, const void* kernel, int lds_limit) {
+  for (const Resident& r : g_raised)
+    if (r.dev == dev && r.kernel == kernel) return;
+  (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_limit);
+  g_raised.push_back(Resident{dev, kernel, 0, 0});
+}
+}  // namespace
+
+void raise_lds_limit(const void* kernel, int lds_limit) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return;
+  std::lock_guard<std::mutex> lock(g_res_mu);
+  raise_locked(dev, kernel, lds_limit);
+}
+
+int64_t resident_workgroups(const void* kernel, int block, size_t dyn_lds, int lds_limit) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  std::lock_guard<std::mutex> lock(g_res_mu);
+  for (const Resident& r : g_resident)
+    if (r.dev == dev && r.kernel == kernel && r.lds == dyn_lds) return r.wgs;
+  if (lds_limit > 0) raise_locked(dev, kernel, lds_limit);
+  int per_cu = 0, cus = 0;
+  const int64_t wgs = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, dyn_lds) == hipSuccess)
+                          ? (int64_t)per_cu * cus : 0;
+  g_resident.push_back(Resident{dev, kernel, dyn_lds, wgs});
+  return wgs;
+}
+
+Switches read_switches() {
+  Switches sw;
+  memset(&sw, 0, sizeof(sw));
+  auto first = [](const char* name) {   // the first character of the variable, 0 when unset or empty
+    const char* e = getenv(name);
+    return e ? e[0] : '\0';
+  };
+  sw.spec_tile = first("FGP_SPEC_TILE") != '0';
+  const char* se = getenv("FGP_SPEC_SLICE_NB");
+  sw.spec_slice_nb = se ? std::max(1, atoi(se)) : 0;
+  sw.spec_persist = first("FGP_SPEC_PERSIST") == '1';   // (opt-in until measured on the device)
+  sw.spec_step_many = first("FGP_SPEC_STEP_MANY") != '0';
+  const char mode = first("FGP_R2C");
+  sw.r2c = mode == '0' ? 0 : (mode == '1' ? 1 : 2);
+  return sw;
 }
 
 // exp(-2 pi i k / 2^logn) for k < count, via sincospi (argument 2k/2^logn is exact).

@@ -709,7 +709,7 @@ constexpr long long kSpecPollMax = 1ll << 22;     // bounded waits of the persis
 constexpr int kPersistLdsMax = 96 * 1024;
 constexpr long long kPersistPollMax = 1ll << 22;
 // the wall-clock bound of one barrier wait of the single-launch fit (device clock ticks: 5e6 = 50 ms at the 100 MHz
-// constant clock of fgp_wall_clock_khz) -- a give-up then costs milliseconds, not 2^22 polls of seconds (ADVICE r05)
+// constant clock of fgp_wall_clock_khz) -- a give-up then costs milliseconds, not 2^22 polls of seconds
 constexpr unsigned long long kPersistWaitTicks = 5000000ull;
 // give-ups of k_spec_persist since load / the last reset (fgp_persist_giveups): never cleared by a launch, so a failure
 // inside a hipGraph replay is still visible after it
@@ -2174,24 +2174,18 @@ __global__ __launch_bounds__(kWG) void k_spec_post_var(Nll a, const double2* __r
   }
 }
 
+// the spectral path's d (1 .. kSpecMaxD) as a compile-time value
 template <typename Fn>
-static int with_spec_d(int d, Fn&& fn) {
-  switch (d) {
-    case 1: return fn(std::integral_constant<int, 1>{});
-    case 2: return fn(std::integral_constant<int, 2>{});
-    case 3: return fn(std::integral_constant<int, 3>{});
-    case 4: return fn(std::integral_constant<int, 4>{});
-    case 5: return fn(std::integral_constant<int, 5>{});
-    case 6: return fn(std::integral_constant<int, 6>{});
-    default: return set_error(kErrUnsupported, "spectral fit path: d = %d > %d", d, kSpecMaxD);
-  }
+static int dispatch_spec_d(int d, Fn&& fn) {
+  const int rc = dispatch_range<1, kSpecMaxD>(d, fn);
+  return rc == kNoMatch ? set_error(kErrUnsupported, "spectral fit path: d = %d > %d", d, kSpecMaxD) : rc;
 }
 
 // Geometry of the spectral iteration for n = 2^log2n, G problems.  Tile kernel (one shared set of spectra,
 // PG <= 4, the chunk's tile <= 32 KB): workgroups of KW = max(CK, main / 512) frequencies, chunks of
 // CK = 64 (4 / PGP).  Otherwise (k_spec_iter): nb k blocks of 64 kpl frequencies covering [0, main)
 // (lattice main = n/2, plus k = n/2; net main = n), PPW problems per wave.
-void spec_geometry(Nll& a, bool allow_tile) {
+void spec_geometry(Nll& a, const Switches& sw, bool allow_tile) {
   const int64_t n = (int64_t)1 << a.log2n;
   const bool net = a.spec_net;
   a.spec_main = net ? n : n / 2;
@@ -2216,8 +2210,7 @@ void spec_geometry(Nll& a, bool allow_tile) {
   a.spec_kw = 0;
   a.spec_ps = 0;
   a.spec_nsl = 1;
-  const char* te = getenv("FGP_SPEC_TILE");   // 0: the per-wave kernel only (A/B experiments)
-  const bool tile_ok = allow_tile && !(te && te[0] == '0');
+  const bool tile_ok = allow_tile && sw.spec_tile;   // FGP_SPEC_TILE=0: the per-wave kernel only (A/B experiments)
   // Tile kernel (one shared set of spectra, d <= 5): 2 problems per wave (1 for G = 1), problem groups
   // PG <= 4 in the 4 waves of a workgroup.  (4 problems per wave at G = 8 -- 233 VGPRs, 2 blocks per
   // workgroup, 1024 blocks -- measured slower: 51.7 vs 42.0 us per C4 iteration, profiles/r03x_*.)
@@ -2251,8 +2244,7 @@ void spec_geometry(Nll& a, bool allow_tile) {
     int64_t snb = std::max<int64_t>(1, a.spec_main / (64 * 64));
     while (snb * nsl < 512 && snb * 2 <= lanes) snb *= 2;
     snb = std::min<int64_t>(snb, a.nb);
-    const char* se = getenv("FGP_SPEC_SLICE_NB");
-    if (se) snb = std::max(1, std::min(a.nb, atoi(se)));
+    if (sw.spec_slice_nb) snb = std::min(a.nb, sw.spec_slice_nb);
     if (pg > 4 && srows * 64 * 8 * kSpecRing <= kSpecLdsMax && srows * 64 <= 512 * kSpecMaxDma &&
         (srows * 64) % 128 == 0 && srows * 64 >= kSpecScratch && a.spec_main % (64 * snb) == 0) {
       a.nb = (int)snb;
@@ -2280,7 +2272,7 @@ void spec_geometry(Nll& a, bool allow_tile) {
 int launch_spec_loss_iter(const Nll& a, hipStream_t st) {
   const int64_t tasks = (int64_t)a.nb * a.G;
   const unsigned grid = (unsigned)((tasks + kWG / 64 - 1) / (kWG / 64));
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     auto go = [&](auto net, auto cv) {
       k_spec_loss_iter<D, decltype(net)::value, decltype(cv)::value><<<grid, kWG, 0, st>>>(a);
@@ -2303,14 +2295,14 @@ int launch_spec_loss_step(const Nll& a, const Fit& f, int iter, int do_update, h
     b.G = a.mt;
     Fit g = f;
     g.per_problem = 0;
-    return with_spec_d(a.d, [&](auto dc) {
+    return dispatch_spec_d(a.d, [&](auto dc) {
       k_spec_loss_step<decltype(dc)::value><<<1, kWG, 0, st>>>(b, g, iter, do_update);
       return check_launch("k_spec_loss_step");
     });
   }
   if (!f.per_problem && a.G > 16) return set_error(kErrUnsupported, "GCV / CV fits: one loss over at most 16 problems");
   if (a.nb > kSpecBlocks) return set_error(kErrInvalid, "k_spec_loss_step: nb > %d", kSpecBlocks);
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     k_spec_loss_step<decltype(dc)::value><<<(unsigned)((a.G + 15) / 16), kWG, 0, st>>>(a, f, iter, do_update);
     return check_launch("k_spec_loss_step");
   });
@@ -2319,7 +2311,7 @@ int launch_spec_loss_step(const Nll& a, const Fit& f, int iter, int do_update, h
 int launch_mt_learn_step(const Nll& a, const Fit& f, int iter, int do_update, hipStream_t st) {
   if (a.mt > kMtMaxT || a.nb > kSpecBlocks || spec_nparams(a) > kSpecScratch)
     return set_error(kErrInvalid, "k_mt_learn_step: shape");
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     k_mt_learn_step<decltype(dc)::value><<<1, kWG, 0, st>>>(a, f, iter, do_update);
     return check_launch("k_mt_learn_step");
   });
@@ -2350,46 +2342,19 @@ int launch_spec_iter(const Nll& a, hipStream_t st, const FitFuse* fz) {
     const size_t shm = sizeof(double) * (size_t)kSpecRing * (size_t)(trows * a.spec_ck);
 #endif
     const unsigned grid = (unsigned)(a.nb / (4 / a.spec_pgp) * a.spec_nsl);
-    return with_spec_d(a.d, [&](auto dc) {
+    return dispatch_spec_d(a.d, [&](auto dc) {
       constexpr int D = decltype(dc)::value;
       if constexpr (D <= 5) {
         auto go = [&](auto kern) {
-          // the ring may exceed the 64 KB default of dynamic LDS: raise each kernel's limit once (one
-          // static for every kernel of this lambda's type: remember which ones)
-          static const void* raised[64];
-          static int nraised = 0;
+          // the ring may exceed the 64 KB default of dynamic LDS
           const void* kp = reinterpret_cast<const void*>(kern);
-          bool done = false;
-          for (int i = 0; i < nraised; ++i) done = done || raised[i] == kp;
-          if (!done) {
-            (void)hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, kSpecLdsMax);
-            if (nraised < 64) raised[nraised++] = kp;
-          }
           if (f.piters > 0) {
-            // persistent: every workgroup must be resident at once (they wait on each other).  The residency
-            // (workgroups per CU x CUs) is queried once per kernel and LDS size and remembered, so a launch
-            // inside a hipGraph capture makes no query.
-            static const void* rk[64];
-            static size_t rshm[64];
-            static int64_t rres[64];
-            static int nr = 0;
-            int64_t resident = -1;
-            for (int i = 0; i < nr; ++i)
-              if (rk[i] == kp && rshm[i] == shm) resident = rres[i];
-            if (resident < 0) {
-              int per_cu = 0, dev = 0, cus = 0;
-              resident = (hipGetDevice(&dev) == hipSuccess &&
-                          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, kWG, shm) == hipSuccess)
-                             ? (int64_t)per_cu * cus : 0;
-              if (nr < 64) {
-                rk[nr] = kp;
-                rshm[nr] = shm;
-                rres[nr++] = resident;
-              }
-            }
-            if (resident < (int64_t)grid) return;    // (rc stays kErrUnsupported: the caller launches per iteration)
+            // persistent: every workgroup must be resident at once (they wait on each other)
+            if (resident_workgroups(kp, kWG, shm, kSpecLdsMax) < (int64_t)grid)
+              return;    // (rc stays kErrUnsupported: the caller launches per iteration)
             persist_ok = true;
+          } else {
+            raise_lds_limit(kp, kSpecLdsMax);
           }
           kern<<<grid, kWG, shm, st>>>(a, f);
         };
@@ -2415,7 +2380,7 @@ int launch_spec_iter(const Nll& a, hipStream_t st, const FitFuse* fz) {
   if (fz) return set_error(kErrInvalid, "spectral iteration: no fused step without the tile kernel");
   const int64_t tasks = (int64_t)a.nb * a.spec_pg;
   const unsigned grid = (unsigned)((tasks + kWG / 64 - 1) / (kWG / 64));
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     auto go = [&](auto net) {
       constexpr bool NET = decltype(net)::value;
@@ -2432,7 +2397,7 @@ int launch_spec_iter(const Nll& a, hipStream_t st, const FitFuse* fz) {
 }
 
 int launch_mt_spec_iter(const Nll& a, hipStream_t st) {
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int DD = decltype(dc)::value;
     if (a.loss == FGP_LOSS_CV && a.mt_learn) k_mt_spec_iter<DD, true, true, true><<<dim3((unsigned)a.nb, (unsigned)a.mt), kWG, 0, st>>>(a);
     else if (a.loss == FGP_LOSS_CV) k_mt_spec_iter<DD, true, true><<<dim3((unsigned)a.nb, (unsigned)a.mt), kWG, 0, st>>>(a);
@@ -2444,7 +2409,7 @@ int launch_mt_spec_iter(const Nll& a, hipStream_t st) {
 }
 
 int launch_spec_reduce_step(const Nll& a, const Fit& f, int iter, int do_update, hipStream_t st) {
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     k_spec_reduce_step<decltype(dc)::value><<<(unsigned)((a.G + 15) / 16), kWG, 0, st>>>(a, f, iter, do_update);
     return check_launch("k_spec_reduce_step");
   });
@@ -2453,41 +2418,13 @@ int launch_spec_reduce_step(const Nll& a, const Fit& f, int iter, int do_update,
 // The k_spec_persist instance of a desc (D, NET), for the residency query.
 static const void* spec_persist_kernel(const Nll& a) {
   const void* kp = nullptr;
-  (void)with_spec_d(a.d, [&](auto dc) {
+  (void)dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     kp = a.spec_net ? reinterpret_cast<const void*>(k_spec_persist<D, true>)
                     : reinterpret_cast<const void*>(k_spec_persist<D, false>);
     return kOk;
   });
   return kp;
-}
-
-// Workgroups of `kp` at `shm` bytes of dynamic LDS that can be resident at once on the current device
-// (workgroups per CU x CUs), queried once per (kernel, LDS size) and remembered -- so a launch inside a hipGraph
-// capture makes no query.  0 when the query fails.
-static int64_t persist_resident(const void* kp, size_t shm) {
-  // keyed by the device too: devices of one process may differ in CU count / partition mode
-  static const void* rk[64];
-  static size_t rshm[64];
-  static int rdev[64];
-  static int64_t rres[64];
-  static int nr = 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 0;
-  for (int i = 0; i < nr; ++i)
-    if (rk[i] == kp && rshm[i] == shm && rdev[i] == dev) return rres[i];
-  (void)hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, kPersistLdsMax);
-  int per_cu = 0, cus = 0;
-  const int64_t resident = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-                            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kp, kWG, shm) == hipSuccess)
-                               ? (int64_t)per_cu * cus : 0;
-  if (nr < 64) {
-    rk[nr] = kp;
-    rshm[nr] = shm;
-    rdev[nr] = dev;
-    rres[nr++] = resident;
-  }
-  return resident;
 }
 
 // Test hook (fgp_set_persist_poll_max): the bound of k_spec_persist's barrier polls (default 2^22), in device memory.
@@ -2509,7 +2446,7 @@ int spec_persist_geometry(const Nll& a, int* W, int* bpw, size_t* shm) {
     if ((size_t)b * per_blk <= (size_t)kPersistLdsMax) {
       // the workgroups wait on each other at the in-kernel grid barrier: all W must be resident at once
       // (a partitioned device, or CUs held by other work, would otherwise turn every barrier into a give-up)
-      if (w > 1 && persist_resident(spec_persist_kernel(a), (size_t)b * per_blk) < (int64_t)w)
+      if (w > 1 && resident_workgroups(spec_persist_kernel(a), kWG, (size_t)b * per_blk, kPersistLdsMax) < (int64_t)w)
         return set_error(kErrUnsupported, "fgp_fit_persist: %d workgroups are not co-resident", w);
       *W = w;
       *bpw = b;
@@ -2544,11 +2481,10 @@ int launch_spec_persist(const Nll& a, const Fit& f, int iters, double logtol, in
   if (hipMemsetAsync(a.partials, 0xff, 3 * sizeof(double) * (size_t)a.nq * (size_t)a.nb, st) != hipSuccess ||
       hipMemsetAsync(out, 0, 3 * sizeof(int), st) != hipSuccess)
     return set_error(kErrHip, "fgp_fit_persist: workspace reset failed");
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     auto go = [&](auto kern) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kPersistLdsMax);
+      raise_lds_limit(reinterpret_cast<const void*>(kern), kPersistLdsMax);
       kern<<<(unsigned)W, kWG, shm, st>>>(a, f, iters, logtol, wait_max, bpw, counter, out);
     };
     if (a.spec_net) go(k_spec_persist<D, true>);
@@ -2565,7 +2501,7 @@ unsigned* spec_step_many_counter(const Nll& a) {
 int launch_spec_step_many(const Nll& a, const Fit& f, int iter, int do_update, hipStream_t st) {
   if (a.nb > kSpecBlocks) return set_error(kErrInvalid, "k_spec_step_many: nb > %d", kSpecBlocks);
   unsigned* counter = spec_step_many_counter(a);
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     k_spec_step_many<decltype(dc)::value><<<(unsigned)((a.G + 15) / 16), kWG, 0, st>>>(a, f, iter, do_update, counter);
     return check_launch("k_spec_step_many");
   });
@@ -2581,7 +2517,7 @@ int spec_counters_offset(const Nll& a, int64_t* off, int* count) {
 RpState spec_scratch_state(const Nll& a, int par) { return spec_state(a, par); }
 
 int launch_spec_finish_step(const Nll& a, const FitFuse& fz, hipStream_t st) {
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     k_spec_finish_step<decltype(dc)::value><<<1, kWG, 0, st>>>(a, fz);
     return check_launch("k_spec_finish_step");
   });
@@ -2609,7 +2545,7 @@ __global__ __launch_bounds__(kWG) void k_spec_post_var_finish(Nll a, const doubl
 int launch_spec_post_var(const Nll& a, const double2* psi, int N, const double* part0, double* out, double* partial,
                          int nblk, int kpl, hipStream_t st) {
   const dim3 grid((unsigned)nblk, (unsigned)((a.G + kSpvPS * (kWG / 64) - 1) / (kSpvPS * (kWG / 64))));
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if constexpr (D <= 4) {
       k_spec_post_var<D><<<grid, kWG, 0, st>>>(a, psi, N, kpl, nblk, partial);
@@ -2627,7 +2563,7 @@ int launch_spec_post_var(const Nll& a, const double2* psi, int N, const double* 
 
 int launch_spec_inv_eig(const Nll& a, double* wa, hipStream_t st) {
   const unsigned grid = (unsigned)((a.spec_K + kWG - 1) / kWG);
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if (a.spec_net) k_spec_inv_eig<D, true><<<grid, kWG, 0, st>>>(a, wa);
     else k_spec_inv_eig<D, false><<<grid, kWG, 0, st>>>(a, wa);
@@ -2638,7 +2574,7 @@ int launch_spec_inv_eig(const Nll& a, double* wa, hipStream_t st) {
 int launch_spec_lam(const Nll& a, hipStream_t st) {
   if (!a.grad_lam) return set_error(kErrInvalid, "fgp_nll_lam: null grad_lam (the output)");
   const dim3 grid((unsigned)((a.spec_K + kWG - 1) / kWG), (unsigned)a.G);
-  return with_spec_d(a.d, [&](auto dc) {
+  return dispatch_spec_d(a.d, [&](auto dc) {
     constexpr int D = decltype(dc)::value;
     if (a.spec_net) k_spec_lam<D, true><<<grid, kWG, 0, st>>>(a);
     else k_spec_lam<D, false><<<grid, kWG, 0, st>>>(a);
@@ -2734,7 +2670,7 @@ int fgp_spec_basis(int family, const double* parts, int64_t parts_stride, int64_
         if (rc != kOk) return rc;
         continue;
       }
-      int rc = with_spec_d(d, [&](auto dc) {
+      int rc = dispatch_spec_d(d, [&](auto dc) {
         k_spec_products<decltype(dc)::value><<<gi, kWG, 0, st>>>(pp, n, s0, cnt, prod);
         return check_launch("k_spec_products");
       });

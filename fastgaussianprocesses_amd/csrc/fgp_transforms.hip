@@ -250,40 +250,26 @@ static int launch_tiny(int m, const void* in, int64_t in_bs, int in_real, void* 
                        int stable, double scale, const double2* tw, hipStream_t st, Pre pre = Pre{nullptr, 0}) {
   const dim3 g((unsigned)((batch + kWG - 1) / kWG));
   const int64_t n = (int64_t)1 << m;
-  switch (m) {
-    case 0: k_tiny<0, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, n, out_real, batch, stable, scale, tw, pre); break;
-    case 1: k_tiny<1, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, n, out_real, batch, stable, scale, tw, pre); break;
-    case 2: k_tiny<2, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, n, out_real, batch, stable, scale, tw, pre); break;
-    case 3: k_tiny<3, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, n, out_real, batch, stable, scale, tw, pre); break;
-    default: return set_error(kErrInvalid, "launch_tiny: bad m");
-  }
-  return check_launch("k_tiny");
+  const int rc = dispatch_range<0, 3>(m, [&](auto pc) {
+    k_tiny<decltype(pc)::value, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, n, out_real, batch, stable, scale, tw,
+                                                           pre);
+    return check_launch("k_tiny");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "launch_tiny: bad m") : rc;
 }
-
-#define FGP_SINGLE_CASE(P)                                                                                   \
-  case P:                                                                                                    \
-    k_single<P, T, ADJ><<<dim3((unsigned)((batch + (kTile >> P) - 1) / (kTile >> P))), kWG, 0, st>>>(      \
-        in, in_bs, in_real, out, (int64_t)1 << P, out_real, batch, stable, scale, tw, pre);                  \
-    break;
 
 template <typename T, bool ADJ>
 static int launch_single(int m, const void* in, int64_t in_bs, int in_real, void* out, int out_real,
                          int64_t batch, int stable, double scale, const double2* tw, hipStream_t st,
                          Pre pre = Pre{nullptr, 0}) {
-  switch (m) {
-    FGP_SINGLE_CASE(4) FGP_SINGLE_CASE(5) FGP_SINGLE_CASE(6) FGP_SINGLE_CASE(7) FGP_SINGLE_CASE(8)
-    FGP_SINGLE_CASE(9) FGP_SINGLE_CASE(10) FGP_SINGLE_CASE(11) FGP_SINGLE_CASE(12)
-    default: return set_error(kErrInvalid, "launch_single: bad m");
-  }
-  return check_launch("k_single");
+  const int rc = dispatch_range<4, 12>(m, [&](auto pc) {
+    constexpr int P = decltype(pc)::value;
+    k_single<P, T, ADJ><<<dim3((unsigned)((batch + (kTile >> P) - 1) / (kTile >> P))), kWG, 0, st>>>(
+        in, in_bs, in_real, out, (int64_t)1 << P, out_real, batch, stable, scale, tw, pre);
+    return check_launch("k_single");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "launch_single: bad m") : rc;
 }
-#undef FGP_SINGLE_CASE
-
-#define FGP_ROWS_CASE(P)                                                                                       \
-  case P:                                                                                                      \
-    k_rows<P, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, out_bs, out_real, m, stable, scale, twiddle, \
-                                         tw, twm);                                                             \
-    break;
 
 template <typename T, bool ADJ>
 static int launch_rows(int m, const void* in, int64_t in_bs, int in_real, void* out, int64_t out_bs, int out_real,
@@ -292,19 +278,13 @@ static int launch_rows(int m, const void* in, int64_t in_bs, int in_real, void* 
   const dim3 g((unsigned)(batch << (m - kTileLog)));
   const double2* tw = tb->tw4096;
   const double2* twm = tb->twm[m];
-  switch (m2) {
-    FGP_ROWS_CASE(9) FGP_ROWS_CASE(10) FGP_ROWS_CASE(11) FGP_ROWS_CASE(12)
-    default: return set_error(kErrInvalid, "launch_rows: bad m2");
-  }
-  return check_launch("k_rows");
+  const int rc = dispatch_range<9, 12>(m2, [&](auto pc) {
+    k_rows<decltype(pc)::value, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, out_bs, out_real, m, stable, scale,
+                                                           twiddle, tw, twm);
+    return check_launch("k_rows");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "launch_rows: bad m2") : rc;
 }
-#undef FGP_ROWS_CASE
-
-#define FGP_COLS_CASE(P)                                                                                       \
-  case P:                                                                                                      \
-    k_cols<P, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, out_bs, out_real, m, stable, scale, twiddle, \
-                                         tw, twm, pre);                                                        \
-    break;
 
 template <typename T, bool ADJ>
 static int launch_cols(int m, const void* in, int64_t in_bs, int in_real, void* out, int64_t out_bs, int out_real,
@@ -314,14 +294,13 @@ static int launch_cols(int m, const void* in, int64_t in_bs, int in_real, void* 
   const dim3 g((unsigned)(batch << (m - kTileLog)));
   const double2* tw = tb->tw4096;
   const double2* twm = tb->twm[m];
-  switch (m1) {
-    FGP_COLS_CASE(4) FGP_COLS_CASE(5) FGP_COLS_CASE(6) FGP_COLS_CASE(7) FGP_COLS_CASE(8)
-    FGP_COLS_CASE(9) FGP_COLS_CASE(10) FGP_COLS_CASE(11) FGP_COLS_CASE(12)
-    default: return set_error(kErrInvalid, "launch_cols: bad m1");
-  }
-  return check_launch("k_cols");
+  const int rc = dispatch_range<4, 12>(m1, [&](auto pc) {
+    k_cols<decltype(pc)::value, T, ADJ><<<g, kWG, 0, st>>>(in, in_bs, in_real, out, out_bs, out_real, m, stable, scale,
+                                                           twiddle, tw, twm, pre);
+    return check_launch("k_cols");
+  });
+  return rc == kNoMatch ? set_error(kErrInvalid, "launch_cols: bad m1") : rc;
 }
-#undef FGP_COLS_CASE
 
 static int validate(const void* in, const void* out, int64_t batch, int log2n, int64_t in_bs) {
   if (log2n < 0 || log2n > kMaxLog2N)

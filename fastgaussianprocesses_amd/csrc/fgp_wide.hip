@@ -595,14 +595,11 @@ int fgp_wide_k1_bwd(const double* parts, int64_t n, int d, const double* scale, 
   hipStream_t st = (hipStream_t)stream;
   const int64_t nblk = (n + kWG - 1) / kWG;
   const dim3 grid((unsigned)nblk, (unsigned)G);
-  switch ((d + 7) / 8) {
-#define FGP_C(DBB) case DBB: k_wide_k1_bwd<DBB><<<grid, kWG, 0, st>>>(parts, n, d, scale, ls, u, nblk, work); break;
-    FGP_C(2) FGP_C(3) FGP_C(4) FGP_C(5) FGP_C(6) FGP_C(7) FGP_C(8)
-#undef FGP_C
-    default: return set_error(kErrInvalid, "fgp_wide_k1_bwd: d=%d", d);
-  }
-  rc = check_launch("k_wide_k1_bwd");
-  if (rc != kOk) return rc;
+  rc = dispatch_range<2, 8>((d + 7) / 8, [&](auto dbc) {
+    k_wide_k1_bwd<decltype(dbc)::value><<<grid, kWG, 0, st>>>(parts, n, d, scale, ls, u, nblk, work);
+    return check_launch("k_wide_k1_bwd");
+  });
+  if (rc != kOk) return rc == kNoMatch ? set_error(kErrInvalid, "fgp_wide_k1_bwd: d=%d", d) : rc;
   k_wide_k1_bwd_sum<<<(unsigned)((int64_t)G * (1 + d)), kWG, 0, st>>>(work, nblk, d, dscale, dls);
   return check_launch("k_wide_k1_bwd_sum");
 }

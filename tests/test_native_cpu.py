@@ -67,6 +67,18 @@ def test_struct_layouts_match_header(tmp_path):
     assert got == expect
 
 
+def test_host_decisions_live_in_the_runtime_only():
+    """The environment switches, the residency query and the dynamic-LDS raise are each decided in one place
+    (csrc/fgp_runtime.hip: read_switches, resident_workgroups, raise_lds_limit): no other source calls the
+    functions they are built on."""
+    csrc = os.path.join(ROOT, "fastgaussianprocesses_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if f.endswith((".hip", ".h")))
+    assert "fgp_runtime.hip" in files and len(files) >= 13
+    for token in ("getenv(", "hipOccupancyMaxActiveBlocksPerMultiprocessor", "hipFuncSetAttribute"):
+        users = [f for f in files if token in open(os.path.join(csrc, f)).read()]
+        assert users == ["fgp_runtime.hip"], "%s used in %s" % (token, users)
+
+
 def test_ops_refuse_cpu_tensors():
     with pytest.raises(RuntimeError, match="HIP device"):
         F.ops.fftbr(torch.zeros(8))
