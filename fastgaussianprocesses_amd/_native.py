@@ -106,7 +106,21 @@ class MtFitDesc(ctypes.Structure):
     ]
 
 
+class WideFitDesc(ctypes.Structure):
+    """Mirror of fgp_wide_fit_desc (include/fgp_hip.h, an addition to ABI 20)."""
+    _fields_ = [
+        ("family", _c_int), ("log2n", _c_int), ("d", _c_int), ("G", _c_int),
+        ("parts", _c_vp), ("parts_stride", _c_i64), ("ysq", _c_vp), ("raw", _c_vp),
+        ("dl", _c_int), ("scale_rg", _c_int), ("ls_rg", _c_int), ("noise_rg", _c_int),
+        ("logdet_weight", _c_dbl), ("mll_const", _c_dbl),
+        ("rprop_prev", _c_vp), ("rprop_step", _c_vp), ("lr", _c_dbl),
+        ("eta_minus", _c_dbl), ("eta_plus", _c_dbl), ("step_min", _c_dbl), ("step_max", _c_dbl),
+        ("loss_hist", _c_vp), ("raw_hist", _c_vp), ("grad_out", _c_vp), ("work", _c_vp),
+    ]
+
+
 _P_NLL = ctypes.POINTER(NllDesc)
+_P_WIDEFIT = ctypes.POINTER(WideFitDesc)
 _P_MTFIT = ctypes.POINTER(MtFitDesc)
 _P_MT = ctypes.POINTER(MtLayout)
 _P_FIT = ctypes.POINTER(FitDesc)
@@ -190,6 +204,9 @@ _SIGNATURES = {
                              _c_vp],
     "fgp_wide_post_mean": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_vp, _c_int, _c_vp,
                            _c_i64, _c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp],
+    # addition to ABI 20: the device-resident wide fit loop
+    "fgp_wide_fit_work": [_P_WIDEFIT, _c_pl],
+    "fgp_wide_fit_run": [_P_WIDEFIT, _c_int, _c_int, _c_int, _c_vp],
 }
 
 

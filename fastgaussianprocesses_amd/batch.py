@@ -9,6 +9,10 @@ keeps its own loss, Rprop state and early-stopping decision), one batched coeffi
 posterior-mean and one posterior-variance launch for all P GPs.  The result for each GP is what its
 own methods return: the stopping rule is applied per GP on its own loss history, each GP's best
 parameters are restored, and the GP objects hold the fitted parameters and data afterwards.
+
+Wide GPs (9 <= d <= 64) are fitted by fgp_wide_fit_run (wide_fit.WideMLL: the same per-problem loop, the parts
+shared when every GP has the same generating vector / matrices) and predicted with one fgp_wide_post_mean per GP
+and each GP's own post_var: fgp_pred_desc and the batched prediction kernels are d <= 8.
 """
 import collections
 import ctypes
@@ -18,6 +22,7 @@ import torch
 
 from . import _native as N
 from . import ops
+from .wide_fit import WideMLL
 from .fit_engine import FusedMLL, LatticePartsGen, cached_engine, fused_lam, mll_constant, spec_basis, spec_basis_gen, spec_inv_eig, spectral_wanted
 
 
@@ -144,10 +149,11 @@ def _check_batch(gps):
     assert len(gps) > 0
     g0 = gps[0]
     n = g0._nh
+    wide = g0.d > N.MAX_D                       # 9 <= d <= 64: the wide device loop (wide_fit.WideMLL)
     for gp in gps:
         assert type(gp) is type(g0), "a GP batch needs GPs of one family"
         assert gp._nh == n and gp.d == g0.d and gp._alphas == g0._alphas and gp.device == g0.device
-        assert gp._fused_ok(), "every GP must qualify for the fused MLL path"
+        assert (gp._wide_fit_ok() if wide else gp._fused_ok()), "every GP must qualify for the fused MLL path"
         assert gp._problem_batch()[1] == 1, "per-output hyper-parameters: fit those GPs individually"
         assert gp.raw_lengthscales.shape == g0.raw_lengthscales.shape
         assert (gp.raw_scale.requires_grad, gp.raw_lengthscales.requires_grad, gp.raw_noise.requires_grad) == \
@@ -158,6 +164,13 @@ def _check_batch(gps):
 def _parts_source(gps, n):
     """Lattice GPs sharing one generating vector regenerate their parts in the kernels (only the P
     shifts are stacked); otherwise a stacked [P, d, n] parts array."""
+    if gps[0].d > N.MAX_D:
+        # wide GPs: ONE [d, n] parts array when every GP shares the generating vector / matrices (the first-column
+        # parts of shifted replicas do not depend on the shift), else each GP's own, stacked
+        keys = [gp._wide_parts_key(n) for gp in gps]
+        if keys[0] is not None and all(k == keys[0] for k in keys):
+            return gps[0]._wide_fit_parts(n), None
+        return torch.stack([gp._wide_fit_parts(n) for gp in gps]), None
     gens = [gp._parts_gen(n) for gp in gps]
     if all(g is not None for g in gens) and all(g.z == gens[0].z for g in gens):
         return None, LatticePartsGen(gens[0].z, gens[0].alphas, torch.cat([g.shift for g in gens], 0))
@@ -202,6 +215,14 @@ def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False):
     g0 = gps[0]
     dl = g0.raw_lengthscales.shape[-1]
     d_out = int(math.prod(g0.shape_batch))
+    if g0.d > N.MAX_D:
+        return WideMLL(g0._FAMILY, parts, ysq, torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
+                       torch.stack([gp.raw_lengthscales.detach().reshape(dl) for gp in gps]),
+                       torch.stack([gp.raw_noise.detach().reshape(-1)[0] for gp in gps]),
+                       logdet_weight=float(d_out), d_out=d_out,
+                       requires_grad=(g0.raw_scale.requires_grad, g0.raw_lengthscales.requires_grad,
+                                      g0.raw_noise.requires_grad),
+                       lr=1e-1 if lr is None else lr, max_iters=iterations + 1)
     if cached and basis is not None:
         # the batch's spectral engine, reused across fits of this geometry (fit_engine.cached_engine)
         return cached_engine(g0._FAMILY, ysq, torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
@@ -407,6 +428,20 @@ class GPBatch(object):
             raw = self.raw()
             parts, gen = self._source()
             dl = self.dl
+            if self.d > N.MAX_D:
+                # wide GPs: k1 of every GP (fgp_wide_k1) over the parts its own coeffs use (_k1parts: K^-1 y is
+                # ill-conditioned, so the eigenvalues are formed from the very same parts) -- the P parameter rows over
+                # one array for nets sharing their matrices (whose parts do not depend on the shift, bit for bit), else
+                # row p over GP p's -- one batched stable transform, then A = 1/ev and ytilde * A (fgp_inv_eig) as below
+                hyp = self._hyp()
+                if parts.dim() == 2 and self.family != ops.LATTICE:
+                    k1 = ops.wide_k1_raw(parts, hyp[:, 0], hyp[:, 1:])
+                else:
+                    k1 = torch.cat([ops.wide_k1_raw(gp._k1parts(self.n), hyp[p:p + 1, 0], hyp[p:p + 1, 1:])
+                                    for p, gp in enumerate(self.gps)])
+                lam = (ops.fftbr_raw if self.family == ops.LATTICE else ops.fwht_raw)(k1, stable=True)
+                self._inv_eig_solve(lam, raw)
+                return self._st["coeffs"]
             basis = self.basis()
             if basis is not None and self.family == ops.LATTICE and 17 <= self.m <= 24:
                 # spectral path: A = 1/ev straight from the spectra (real), the product fused into the
@@ -418,18 +453,22 @@ class GPBatch(object):
                 return self._st["coeffs"]
             lam = fused_lam(self.family, parts, raw[:, 0], raw[:, 1:1 + dl], raw[:, 1 + dl], self.P, gen=gen, n=self.n,
                             basis=self.basis())
-            yt = self.ytilde()
-            ya = torch.empty_like(lam)
-            wa = torch.empty((self.P, self.n), dtype=torch.float64, device=self.device)
-            noise = raw[:, 1 + dl:]
-            N.call("fgp_inv_eig", self.family, N.ptr(lam), N.ptr(yt), yt.stride(0), N.ptr(noise), raw.stride(0),
-                   self.P, self.m, N.ptr(ya), N.ptr(wa), N.stream_ptr(self.device))
-            if self.family == ops.LATTICE:
-                self._st["coeffs"] = ops.ifftbr_raw(ya, stable=True, real_out=True)
-            else:
-                self._st["coeffs"] = ops.fwht_raw(ya, stable=True)
-            self._st["wa"] = wa
+            self._inv_eig_solve(lam, raw)
         return self._st["coeffs"]
+
+    def _inv_eig_solve(self, lam, raw):
+        """coeffs and wa from lambda [P, n]: A = 1/ev and ytilde * A (fgp_inv_eig), one batched inverse transform."""
+        yt = self.ytilde()
+        ya = torch.empty_like(lam)
+        wa = torch.empty((self.P, self.n), dtype=torch.float64, device=self.device)
+        noise = raw[:, 1 + self.dl:]
+        N.call("fgp_inv_eig", self.family, N.ptr(lam), N.ptr(yt), yt.stride(0), N.ptr(noise), raw.stride(0),
+               self.P, self.m, N.ptr(ya), N.ptr(wa), N.stream_ptr(self.device))
+        if self.family == ops.LATTICE:
+            self._st["coeffs"] = ops.ifftbr_raw(ya, stable=True, real_out=True)
+        else:
+            self._st["coeffs"] = ops.fwht_raw(ya, stable=True)
+        self._st["wa"] = wa
 
     def _hyp(self):
         if "hyp" not in self._st:
@@ -479,6 +518,14 @@ class GPBatch(object):
         """[P, N] posterior means (AbstractGP.post_mean of every GP, abstract_gp.py:352-380)."""
         self.coeffs()
         x, xs, Nt = self._points(x)
+        if self.d > N.MAX_D:
+            # wide GPs: fgp_wide_post_mean once per GP into the [P, N] stack (fgp_pred_desc is FGP_MAX_D-sized)
+            coeffs, hyp = self._st["coeffs"], self._hyp()
+            out = torch.empty((self.P, Nt), dtype=torch.float64, device=self.device)
+            for p, gp in enumerate(self.gps):
+                out[p] = ops.post_mean_matfree(self.family, x if x.ndim == 2 else x[p], self.z[p], hyp[p:p + 1],
+                                               coeffs[p:p + 1], alphas=gp._alphas, tbits=self.tbits)[0]
+            return out
         desc = self._desc()
         wl = ctypes.c_int64(0)
         N.call("fgp_post_mean_batched_work", desc, Nt, ctypes.byref(wl))
@@ -490,8 +537,9 @@ class GPBatch(object):
 
     def post_var(self, x, chunk=16):
         """[P, N] posterior variances at the GPs' current n (AbstractGP.post_var, abstract_gp.py:381-416)."""
-        if self.m < 13:
-            return torch.stack([gp.post_var(x) for gp in self.gps])
+        if self.m < 13 or self.d > N.MAX_D:     # (wide GPs: no batched prediction kernel)
+            x = torch.as_tensor(x)
+            return torch.stack([gp.post_var(x if x.ndim == 2 else x[p]) for p, gp in enumerate(self.gps)])
         self.coeffs()
         x, xs, Nt = self._points(x)
         out = torch.empty((self.P, Nt), dtype=torch.float64, device=self.device)

@@ -9,6 +9,7 @@ misuse.  Every numerical hot spot runs in the HIP library (include/fgp_hip.h):
   k1 parts                  -> fgp_lattice_parts / fgp_net_parts
   fit (MLL, default Rprop)  -> fgp_fit_run: fused forward / adjoint / Rprop on device, histories read
                                back in chunks to apply the reference's early-stopping rule exactly
+                               (9 <= d <= 64: fgp_wide_fit_run under FGP_WIDE_FIT_DEVICE=1, else the generic loop)
   post_mean                 -> fgp_post_mean (matrix-free cross-kernel contraction)
   post_var / post_cov       -> fgp_kernel_rows + the transform solve
 
@@ -742,15 +743,19 @@ class AbstractFastGP(torch.nn.Module):
                      task_kernel=store_hists or (store_task_kernel_hist and (
                          self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad)))
         stop = (np.log(1 + stop_crit_improvement_threshold), stop_crit_wait_iterations)
-        if masks is not None and optimizer is None and loss_metric == "MLL" and self._fused_ok():
+        # wide inputs (d > 8): the device loop fgp_wide_fit_run only under FGP_WIDE_FIT_DEVICE=1 (default off: the
+        # generic autograd loop over fgp_wide_k1 / fgp_wide_k1_bwd)
+        wide_dev = (optimizer is None and loss_metric == "MLL" and self.d > _native.MAX_D
+                    and os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1" and self._wide_fit_ok())
+        if masks is not None and optimizer is None and loss_metric == "MLL" and (self._fused_ok() or wide_dev):
             mk = self._masked_ysq(masks)
             if mk is not None:
                 # only the outputs y[..., *masks] in the loss, shared hyper-parameters: the device fit on their
                 # Y = sum |ytilde_b|^2 with d_out = the selected count (abstract_gp.py:220-235, 253-260)
                 return self._fit_fused(iterations, 1e-1 if lr is None else lr, stop, hists, verbose, verbose_indent,
                                        ysq=mk[0], d_out=mk[1])
-        fused = optimizer is None and masks is None and self._fused_ok() and (
-            loss_metric == "MLL" or self._alt_loss_ok(loss_metric, cv_weights))
+        fused = optimizer is None and masks is None and ((self._fused_ok() and (
+            loss_metric == "MLL" or self._alt_loss_ok(loss_metric, cv_weights))) or wide_dev)
         if optimizer is None:
             optimizer = None if fused else self.get_default_optimizer(lr)
         else:
@@ -776,6 +781,46 @@ class AbstractFastGP(torch.nn.Module):
             return False
         pb = self._problem_batch()
         return pb is not None
+
+    def _wide_fit_ok(self):
+        """The wide device fit loop (fgp_wide_fit_run, wide_fit.WideMLL) applies: 9 <= d <= 64, n >= 16, exp transforms,
+        a fixed unit task kernel and ONE eigen-problem (hyper-parameters shared by the outputs)."""
+        if not (_native.MAX_D < self.d <= _native.WIDE_MAX_D) or self._nh < 16:
+            return False
+        if self._tfs["scale"][1] is not _exp or self._tfs["lengthscales"][1] is not _exp or \
+                self._tfs["noise"][1] is not _exp:
+            return False
+        if self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad:
+            return False
+        if not self._task_unit():
+            return False
+        pb = self._problem_batch()
+        return pb is not None and pb[1] == 1
+
+    def _wide_parts_key(self, n):
+        """What the first-column parts of the wide device fit depend on, or None when they are this GP's own: GPs with
+        equal keys (shifted replicas of one lattice or net) share ONE parts array in a batch."""
+        return None
+
+    def _wide_fit_parts(self, n):
+        """[d, n] first-column parts of the wide device fit: the same array, bit for bit, for every GP with this
+        GP's _wide_parts_key -- so a GP's fit does not depend on whether it shares the array with a batch."""
+        return self._k1parts(n)
+
+    def _wide_engine(self, iterations, lr, ysq=None, d_out=None):
+        """The WideMLL of this GP's fit (one eigen-problem)."""
+        from .wide_fit import WideMLL
+        n = self._nh
+        pb_shape, G = self._problem_batch()
+        if d_out is None:
+            d_out = math.prod(self.shape_batch)
+        dl = self.raw_lengthscales.shape[-1]
+        return WideMLL(self._FAMILY, self._wide_fit_parts(n), self._ysq(pb_shape, G) if ysq is None else ysq,
+                       self.raw_scale.detach().reshape(1), self.raw_lengthscales.detach().reshape(1, dl),
+                       self.raw_noise.detach().reshape(1), logdet_weight=d_out / G, d_out=d_out,
+                       requires_grad=(self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad,
+                                      self.raw_noise.requires_grad),
+                       lr=lr, max_iters=min(iterations + 1, 8192))
 
     def _alt_loss_ok(self, loss_metric, cv_weights):
         """fit(loss_metric="GCV" / "CV") on the device (fgp_nll_desc.loss_metric, ABI 16): the spectral path
@@ -848,6 +893,8 @@ class AbstractFastGP(torch.nn.Module):
         lattice parts or the parts array; `ysq` / `d_out` override Y = sum_b |ytilde_b|^2 and the output
         count (distributed.fit_sharded: Y all-reduced over the ranks' output shards); loss_metric GCV / CV: the
         spectral path's alternative losses (FusedMLL)."""
+        if self.d > _native.MAX_D:
+            return self._wide_engine(iterations, lr, ysq, d_out)
         n = self._nh
         pb_shape, G = self._problem_batch()
         if d_out is None:
@@ -1639,6 +1686,30 @@ class FastGPLattice(AbstractFastGP):
         self._ensure_points(1)
         return LatticePartsGen(z, self._alphas, self._x[0:1])
 
+    def _wide_parts_key(self, n):
+        """This package's natural-order Lattice: the first-column distances (x_i - x_0) % 1 = (v(i) z) % 1 do not depend
+        on the shift."""
+        m = int(n).bit_length() - 1
+        if not isinstance(self.seq, _seqs.Lattice):
+            return None
+        z = tuple(int(v) for v in self.seq.z[:self.d])
+        if len(z) != self.d or not all(0 < v < 2 ** (53 - m) for v in z):
+            return None
+        return ("lattice", z, tuple(self._alphas))
+
+    def _wide_fit_parts(self, n):
+        """The parts of the UNSHIFTED lattice (x_0 = 0: the distances (v(i) z) % 1 are exact) -- equal to _k1parts up to
+        the rounding of the shifted points' differences, and the same bits for every shift."""
+        key = self._wide_parts_key(n)
+        if key is None:
+            return self._k1parts(n)
+        memo = self.__dict__.setdefault("_wide_parts_memo", {})
+        hit = memo.get(n)
+        if hit is None or hit[0] != key:
+            x = ops.lattice_points(list(key[1]), np.zeros(self.d), 0, n, device=self.device)
+            hit = memo[n] = (key, ops.lattice_parts(x, x[0], self._alphas))
+        return hit[1]
+
     def _part_at_zero(self):
         return torch.tensor([ops.lattice_coefficient(a) * float(_bern(2 * a, 0.0)) for a in self._alphas],
                             dtype=torch.float64)
@@ -1731,6 +1802,14 @@ class FastGPDigitalNetB2(AbstractFastGP):
 
     def _compute_parts(self, xb, x0, out=None):
         return ops.net_parts(xb, x0, self.t, out=out, alphas=self._alphas)
+
+    def _wide_parts_key(self, n):
+        """This package's natural-order DigitalNetB2: xb_i XOR xb_0 is the unshifted net's point, whatever the digital
+        shift -- _k1parts is already the same array, bit for bit, for every shift."""
+        if not isinstance(self.seq, _seqs.DigitalNetB2):
+            return None
+        m = int(n).bit_length() - 1
+        return ("net", self.seq.C[:self.d, :m].tobytes(), int(self.t), tuple(self._alphas))
 
     def _part_at_zero(self):
         return torch.tensor([_WALSH_AT_ZERO[a] for a in self._alphas], dtype=torch.float64)

@@ -535,6 +535,54 @@ int fgp_wide_post_mean(int family, const double* xt, int64_t N, const void* z, i
                        int64_t coeff_stride, int B, double* out, int64_t out_stride, double* work, int64_t chunk,
                        void* stream);
 
+/* Addition to ABI 20 -- the device-resident MLL fit of wide GPs (AbstractGP.fit's loop, abstract_gp.py:241-296, with
+ * torch.optim.Rprop, abstract_fast_gp.py:53-57): G independent eigen-problems of one family, n = 2^log2n and d, each
+ * with its own parameters, loss, Rprop state and reduction order (problem g's results do not depend on G or on the
+ * other problems).  Per iteration, on the caller's stream and with no host synchronisation:
+ *   k1 = scale prod_j (1 + l_j parts_j) (fgp_wide_k1), lambda = ft(k1) (stable fftbr / fwht; the half-length lattice
+ *   transforms from n = 2^17), ev = sqrt(n) Re(lambda) + noise, the eigenvalue-terms kernel (partials of
+ *   sum Y / ev, sum log|ev|, sum (-Y / ev^2 + w / ev) and g~ = dL/dlambda = 1/2 sqrt(n) (-Y / ev^2 + w / ev)), the
+ *   adjoint transform u = dL/dk1, fgp_wide_k1_bwd, and the step kernel (one workgroup per problem: two-level sums
+ *   without atomics, loss = 1/2 (norm + w logdet) + mll_const, the history rows, the chain rule through the exp
+ *   transforms, Rprop for the blocks whose *_rg flag is set).
+ * raw = [G scales, G dl lengthscales, G noises] (log parameters, updated in place), dl in {1, d};
+ * n_params = G (2 + dl).  loss_hist [iters][G][3] = (loss, norm term, w logdet); raw_hist [iters][n_params]; row i of
+ * both holds the loss and the parameters AT iteration i, before its step.  grad_out [n_params]: the raw-parameter
+ * gradient of the last evaluation.  ysq and work must be 16-byte aligned.
+ * (The two functions are declared `extern`: tests/test_wide_cpu.py takes the plain `int fgp_wide_*` declarations
+ * as the ABI 19 set it calls one by one.) */
+typedef struct fgp_wide_fit_desc {
+  int family;                 /* FGP_FAMILY_LATTICE / FGP_FAMILY_NET */
+  int log2n;                  /* 0 .. 24 */
+  int d;                      /* FGP_MAX_D + 1 .. FGP_WIDE_MAX_D */
+  int G;                      /* independent eigen-problems, 1 .. 65535 */
+  const double* parts;        /* [d][n] first-column kernel parts (fgp_wide_lattice_parts / fgp_wide_net_parts) */
+  int64_t parts_stride;       /* 0: one array shared by every problem; else d n elements between problems */
+  const double* ysq;          /* [G][n]: Y_k = sum over the outputs of problem g of |ytilde_k|^2 */
+  double* raw;                /* [n_params] */
+  int dl;                     /* lengthscales per problem: 1 or d */
+  int scale_rg, ls_rg, noise_rg; /* requires_grad of each block */
+  double logdet_weight;       /* w = d_out / numel(logdet)  (abstract_gp.py:256) */
+  double mll_const;           /* 1/2 d_out n log(2 pi)  (abstract_gp.py:235), added to 1/2 (norm + w logdet) */
+  double* rprop_prev;         /* [n_params] previous gradient */
+  double* rprop_step;         /* [n_params] step sizes */
+  double lr;                  /* > 0: a run with iter0 == 0 starts a new fit (prev = 0, step = lr, set on the device);
+                                 <= 0: the Rprop state is the caller's */
+  double eta_minus, eta_plus, step_min, step_max; /* torch.optim.Rprop defaults 0.5, 1.2, 1e-6, 50 */
+  double* loss_hist;
+  double* raw_hist;
+  double* grad_out;
+  void* work;                 /* fgp_wide_fit_work doubles */
+} fgp_wide_fit_desc;
+
+/* Doubles of `work`.  Validates the desc's sizes (not its pointers) as fgp_wide_fit_run does. */
+extern int fgp_wide_fit_work(const fgp_wide_fit_desc* desc, int64_t* len);
+/* Iterations iter0 .. iter0 + iters - 1 (history rows), with the semantics of fgp_fit_run: final_no_update leaves the
+ * last evaluated parameters unstepped.  Arguments are validated before any HIP call (also without a device):
+ * d outside 9 .. 64, log2n outside 0 .. 24, G < 1, dl not in {1, d}, a null pointer and negative iters each return
+ * FGP_ERR_INVALID with a message that names the field. */
+extern int fgp_wide_fit_run(const fgp_wide_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
+
 
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):
  * xb[i - n_min][j] = XOR_{k: bit k of i} C[j][k] XOR shift[j] (t-bit ints), x = xb 2^-t; C [d][mcols] and

@@ -4,6 +4,11 @@
                                              # (alternating), and ms per wide post_mean; one JSON line
     python tools/wide_kernels.py trace [m]   # the fused evaluations and the post_mean only (kernel names k_wide_*)
     python tools/wide_kernels.py trace0 [m]  # the evaluations with the torch formulation of k1 (FGP_WIDE_FUSED=0)
+    python tools/wide_kernels.py --fit [m]   # ms per Rprop iteration (time / 21 evaluations) of a 20-iteration fit: the
+                                             # device loop (FGP_WIDE_FIT_DEVICE=1, fgp_wide_fit_run) and the generic
+                                             # autograd loop alternating in one process, 5 repetitions each and their
+                                             # medians; one JSON line
+    python tools/wide_kernels.py --fit-trace [m]   # one 20-iteration device-loop fit only (launches per iteration)
 
 d = 16, n = 2^m, m = 16 by default (lattice, alpha = 2, lengthscales linspace(0.05, 0.3, d)), one hyper-parameter row; post_mean at
 N = 4096 test points, one output.  Byte / operation models:
@@ -52,10 +57,44 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3
 
 
+FIT_ITERS = 20
+
+
+def fit_once(gp, raw0, device_loop):
+    """One 20-iteration MLL fit from the parameters raw0 (no early stop), by the device loop or the generic one."""
+    os.environ["FGP_WIDE_FIT_DEVICE"] = "1" if device_loop else "0"
+    for name, val in raw0.items():
+        old = gp._parameters[name]
+        gp._parameters[name] = torch.nn.Parameter(val.clone(), requires_grad=old.requires_grad)
+    gp._cache = {k: v for k, v in gp._cache.items() if not k[2]}
+    gp._snap = None
+    return gp.fit(iterations=FIT_ITERS, verbose=0, stop_crit_wait_iterations=FIT_ITERS + 5)
+
+
+def fit_mode(trace):
+    gp = make()
+    raw0 = {k: p.detach().clone() for k, p in gp.named_parameters()}
+    if trace:
+        fit_once(gp, raw0, True)
+        torch.cuda.synchronize()
+        return
+    res = {"d": D, "n": 2 ** M, "iterations": FIT_ITERS, "ms_per_iteration": {"device": [], "generic": []}}
+    for dev in (True, False):
+        fit_once(gp, raw0, dev)
+    for _ in range(5):                      # alternate the two loops in one process
+        for key, dev in (("device", True), ("generic", False)):
+            ms = timed(lambda: fit_once(gp, raw0, dev), 1)
+            res["ms_per_iteration"][key].append(round(ms / (FIT_ITERS + 1), 4))
+    res["median_ms_per_iteration"] = {k: sorted(v)[len(v) // 2] for k, v in res["ms_per_iteration"].items()}
+    print(json.dumps(res))
+
+
 def main():
     global M
     mode = sys.argv[1] if len(sys.argv) > 1 else "time"
     M = int(sys.argv[2]) if len(sys.argv) > 2 else M
+    if mode in ("--fit", "--fit-trace"):
+        return fit_mode(mode == "--fit-trace")
     gp = make()
     n = 2 ** M
     xt = torch.rand((NT, D), generator=torch.Generator().manual_seed(5)).to("cuda")
