@@ -24,6 +24,7 @@ from . import _native as N
 from . import ops
 from .wide_fit import WideMLL
 from .fit_engine import FusedMLL, LatticePartsGen, cached_engine, fused_lam, mll_constant, spec_basis, spec_basis_gen, spec_inv_eig, spectral_wanted
+from .fit_loop import StopRule, chunk_schedule, first_minimum
 
 
 class _LossReader(object):
@@ -53,60 +54,46 @@ class _LossReader(object):
 
 
 def _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations):
-    """AbstractGP.fit's iteration / early-stopping rule (fastgps/abstract_gp.py:241-289) applied per
-    problem of a per_problem FusedMLL.  Chunks of iterations are enqueued ahead while no problem can
-    have stopped before them (a problem that has waited w iterations stops at the earliest after
-    wait - w more), so the host reads losses without draining the device queue; iterations a problem
-    runs after its stop are discarded (its parameters are restored from the history)."""
-    logtol = math.log(1 + stop_crit_improvement_threshold)
-    wait_max = stop_crit_wait_iterations
+    """AbstractGP.fit's iteration / early-stopping rule (fit_loop.StopRule) applied per problem of a per_problem
+    engine.  Chunks of iterations are enqueued ahead while no problem can have stopped before them (a problem that
+    has waited w iterations stops at the earliest after wait - w more), so the host reads losses without draining the
+    device queue; iterations a problem runs after its stop are discarded (its parameters are restored from the history).
+    Returns every problem's last iteration, best iteration and losses -- when no problem can stop early, the best
+    iterations as ONE device tensor [P] and no losses: nothing is decided on the host, so there is no host sync."""
     P = eng.G
+    stop = (iterations, math.log(1 + stop_crit_improvement_threshold), stop_crit_wait_iterations)
     total = iterations + 1
     eng.ensure_history(total)
-    if wait_max > iterations:
-        # no problem can stop early: every one runs to `iterations` and restores its best iterate
-        # (the first minimum of its loss history).  Nothing to decide on the host -> no host sync; the
-        # best iterations are found on the device (_best_raw) and losses are copied back only on request.
+    if not StopRule(*stop).can_stop_early:
         eng.run(0, total, final_no_update=True)
-        return [dict(stop=iterations, best_i=None, losses=None, p=p, eng=eng) for p in range(P)]
+        return [iterations] * P, first_minimum(eng.loss_hist[:total, :, 0]), None
+    rules = [StopRule(*stop) for _ in range(P)]
     reader = _LossReader(eng.device)
-    state = [dict(best=math.inf, save=math.inf, waited=0, best_i=0, stop=None, losses=[]) for _ in range(P)]
+    losses = [[] for _ in range(P)]
+    chunks = chunk_schedule(total)
     pending = collections.deque()
     enq = read = 0
-    chunk = 4
-    while True:
-        active = [s for s in state if s["stop"] is None]
-        if not active:
-            break
-        while enq < total and (enq == read or all(wait_max - s["waited"] > enq - read for s in active)):
-            k = min(chunk, total - enq)
-            eng.run(enq, k, final_no_update=(enq + k == total))
-            pending.append((enq, k, reader.submit(eng.loss_hist[enq:enq + k])))
+    while any(r.stop is None for r in rules):
+        active = [r for r in rules if r.stop is None]
+        while enq < total and (enq == read or all(r.wait_max - r.waited > enq - read for r in active)):
+            i0, k, last = next(chunks)
+            eng.run(i0, k, final_no_update=last)
+            pending.append((i0, k, reader.submit(eng.loss_hist[i0:i0 + k])))
             enq += k
-            chunk = min(64, chunk * 2)
         i0, k, item = pending.popleft()
         lh = _LossReader.get(item)
-        for p, s in enumerate(state):
-            if s["stop"] is not None:
+        for p, rule in enumerate(rules):
+            if rule.stop is not None:
                 continue
             for r in range(k):
-                i = i0 + r
                 lv = float(lh[r, p, 0])
-                s["losses"].append(lv)
-                if lv < s["best"]:
-                    s["best"], s["best_i"] = lv, i
-                if (s["save"] - lv) > logtol:
-                    s["waited"] = 0
-                    s["save"] = s["best"]
-                else:
-                    s["waited"] += 1
-                if i == iterations or s["waited"] == wait_max:
-                    s["stop"] = i
+                losses[p].append(lv)
+                if rule.push(i0 + r, lv):
                     break
         read = i0 + k
     for _, _, item in pending:          # drain speculative chunks' copies
         _LossReader.get(item)
-    return state
+    return [r.stop for r in rules], [r.best_i for r in rules], losses
 
 
 _COLS = {}
@@ -124,23 +111,18 @@ def _best_cols(device, P, S, L, dl):
     return _COLS[key]
 
 
-def _best_raw(eng, state, dl):
-    """[P, 2 + dl] = (raw scale, raw lengthscales, raw noise) of every problem at its best iteration
-    (one gather from the per-iteration parameter history).  Best iterations decided on the device
-    (best_i None: the first minimum of each loss history, = the host rule `lv < best`) stay there."""
+def _best_raw(eng, best, dl):
+    """[P, 2 + dl] = (raw scale, raw lengthscales, raw noise) of every problem at its best iteration `best` (one gather
+    from the per-iteration parameter history); best iterations decided on the device (a tensor) stay there."""
     P = eng.G
     S, L, _ = eng.sizes
     idx_c = _best_cols(eng.device, P, S, L, dl)
-    if state[0]["best_i"] is None:
-        total = state[0]["stop"] + 1
-        lh = eng.loss_hist[:total, :, 0]
-        lh = torch.where(torch.isnan(lh), torch.full_like(lh, math.inf), lh)   # NaN never becomes best
-        best = lh.argmin(0)                                                 # [P], first minimum
+    if torch.is_tensor(best):
         idx_r = best.repeat_interleave(2 + dl)
     else:
         rows = []
-        for s in state:
-            rows += [s["best_i"]] * (2 + dl)
+        for b in best:
+            rows += [b] * (2 + dl)
         idx_r = torch.tensor(rows, dtype=torch.int64).pin_memory().to(eng.device, non_blocking=True)
     return eng.raw_hist[idx_r, idx_c].reshape(P, 2 + dl)
 
@@ -156,8 +138,7 @@ def _check_batch(gps):
         assert (gp._wide_fit_ok() if wide else gp._fused_ok()), "every GP must qualify for the fused MLL path"
         assert gp._problem_batch()[1] == 1, "per-output hyper-parameters: fit those GPs individually"
         assert gp.raw_lengthscales.shape == g0.raw_lengthscales.shape
-        assert (gp.raw_scale.requires_grad, gp.raw_lengthscales.requires_grad, gp.raw_noise.requires_grad) == \
-               (g0.raw_scale.requires_grad, g0.raw_lengthscales.requires_grad, g0.raw_noise.requires_grad)
+        assert gp._raw_requires_grad() == g0._raw_requires_grad()
     return g0, n
 
 
@@ -215,48 +196,27 @@ def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False):
     g0 = gps[0]
     dl = g0.raw_lengthscales.shape[-1]
     d_out = int(math.prod(g0.shape_batch))
+    raw = (torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
+           torch.stack([gp.raw_lengthscales.detach().reshape(dl) for gp in gps]),
+           torch.stack([gp.raw_noise.detach().reshape(-1)[0] for gp in gps]))
+    kw = dict(logdet_weight=float(d_out), requires_grad=g0._raw_requires_grad(), lr=1e-1 if lr is None else lr,
+              max_iters=iterations + 1)
     if g0.d > N.MAX_D:
-        return WideMLL(g0._FAMILY, parts, ysq, torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
-                       torch.stack([gp.raw_lengthscales.detach().reshape(dl) for gp in gps]),
-                       torch.stack([gp.raw_noise.detach().reshape(-1)[0] for gp in gps]),
-                       logdet_weight=float(d_out), d_out=d_out,
-                       requires_grad=(g0.raw_scale.requires_grad, g0.raw_lengthscales.requires_grad,
-                                      g0.raw_noise.requires_grad),
-                       lr=1e-1 if lr is None else lr, max_iters=iterations + 1)
+        return WideMLL(g0._FAMILY, parts, ysq, *raw, d_out=d_out, **kw)
+    kw.update(mll_const=mll_constant(d_out, n), basis=basis, per_problem=True)
     if cached and basis is not None:
         # the batch's spectral engine, reused across fits of this geometry (fit_engine.cached_engine)
-        return cached_engine(g0._FAMILY, ysq, torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
-                             torch.stack([gp.raw_lengthscales.detach().reshape(dl) for gp in gps]),
-                             torch.stack([gp.raw_noise.detach().reshape(-1)[0] for gp in gps]),
-                             logdet_weight=float(d_out), mll_const=mll_constant(d_out, n),
-                             requires_grad=(g0.raw_scale.requires_grad, g0.raw_lengthscales.requires_grad,
-                                            g0.raw_noise.requires_grad),
-                             lr=1e-1 if lr is None else lr, max_iters=iterations + 1, basis=basis, per_problem=True)
-    return FusedMLL(g0._FAMILY, parts, ysq,
-                    torch.stack([gp.raw_scale.detach().reshape(-1)[0] for gp in gps]),
-                    torch.stack([gp.raw_lengthscales.detach().reshape(dl) for gp in gps]),
-                    torch.stack([gp.raw_noise.detach().reshape(-1)[0] for gp in gps]),
-                    logdet_weight=float(d_out), mll_const=mll_constant(d_out, n),
-                    requires_grad=(g0.raw_scale.requires_grad, g0.raw_lengthscales.requires_grad,
-                                   g0.raw_noise.requires_grad),
-                    lr=1e-1 if lr is None else lr, max_iters=iterations + 1, parts_per_problem=True,
-                    per_problem=True, gen=None if basis is not None else gen,
-                    basis=basis)
+        return cached_engine(g0._FAMILY, ysq, *raw, **kw)
+    return FusedMLL(g0._FAMILY, parts, ysq, *raw, parts_per_problem=True, gen=None if basis is not None else gen, **kw)
 
 
-def _fit_data(state, store):
-    out = []
-    lh = None
-    for s in state:
-        data = {"iterations": s["stop"]}
-        if store:
-            if s["losses"] is None:          # device-decided run: copy the histories back now
-                if lh is None:
-                    lh = s["eng"].loss_hist[:s["stop"] + 1, :, 0].cpu()
-                data["loss_hist"] = -lh[:, s["p"]].clone()
-            else:
-                data["loss_hist"] = torch.tensor([-v for v in s["losses"]])
-        out.append(data)
+def _fit_data(eng, stops, losses, store):
+    """The per-GP data dicts of _fit_loop's result (losses None: the histories are still on the device)."""
+    out = [{"iterations": s} for s in stops]
+    if store:
+        lh = eng.loss_hist[:stops[0] + 1, :, 0].cpu() if losses is None else None
+        for p, data in enumerate(out):
+            data["loss_hist"] = -lh[:, p].clone() if losses is None else torch.tensor([-v for v in losses[p]])
     return out
 
 
@@ -267,9 +227,9 @@ def fit_batched(gps, iterations=5000, lr=None, stop_crit_improvement_threshold=5
     Returns the list of per-GP `data` dicts that `gp.fit(iterations=..., verbose=0, ...)` would return."""
     g0, n = _check_batch(gps)
     eng = batched_engine(gps, iterations, lr)
-    state = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
-    _set_raw(gps, _best_raw(eng, state, g0.raw_lengthscales.shape[-1]).clone(), g0.raw_lengthscales.shape[-1])
-    return _fit_data(state, store_hists or store_loss_hist)
+    stops, best, losses = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
+    _set_raw(gps, _best_raw(eng, best, g0.raw_lengthscales.shape[-1]).clone(), g0.raw_lengthscales.shape[-1])
+    return _fit_data(eng, stops, losses, store_hists or store_loss_hist)
 
 
 def batched_engine(gps, iterations, lr=None):
@@ -412,11 +372,11 @@ class GPBatch(object):
         per-GP data dicts."""
         parts, gen = self._source()
         eng = _engine(self.gps, self.n, self.ysq(), parts, gen, lr, iterations, basis=self.basis(), cached=True)
-        state = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
-        best = _best_raw(eng, state, self.dl)
+        stops, best_i, losses = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
+        best = _best_raw(eng, best_i, self.dl)
         self.set_raw(best)
         self._st["raw"] = best
-        out = _fit_data(state, store_hists or store_loss_hist)
+        out = _fit_data(eng, stops, losses, store_hists or store_loss_hist)
         eng.release_inputs()
         return out
 

@@ -31,6 +31,7 @@ from . import ops
 from . import seqs as _seqs
 from .fit_engine import (SPEC_MAX_D, FusedMLL, LatticePartsGen, cached_engine, mll_constant, spec_basis, spec_basis_gen,
                          spec_inv_eig, spec_k, spec_post_var, spectral_wanted)
+from .fit_loop import (FitLog, StopRule, fit_all_rows, fit_chunked, fit_persist, fit_persist_deferred, hist_flags)
 
 
 def _log(x):
@@ -142,8 +143,8 @@ class AbstractFastGP(torch.nn.Module):
     _FTOUTDTYPE = None
     _MULTITASK = False
     # host-side attributes the fit / ingest path reassigns on every call (never Parameters, buffers or sub-modules)
-    _PLAIN_ATTRS = frozenset(("_cache", "_snap", "_nh", "_y", "_yt_state", "_n_t", "_m_t", "_iters_for_log",
-                              "_pgen_memo", "_task_unit_memo", "_pts_T", "_pts_n", "_x", "_xb"))
+    _PLAIN_ATTRS = frozenset(("_cache", "_snap", "_nh", "_y", "_yt_state", "_n_t", "_m_t", "_pgen_memo",
+                              "_task_unit_memo", "_pts_T", "_pts_n", "_x", "_xb"))
 
     def __new__(cls, *args, **kwargs):
         if not cls._MULTITASK and cls._FAMILY is not None and _wants_multitask(cls, args, kwargs):
@@ -723,10 +724,13 @@ class AbstractFastGP(torch.nn.Module):
             stop_crit_wait_iterations=10, store_hists=False, store_loss_hist=False, store_scale_hist=False,
             store_lengthscales_hist=False, store_noise_hist=False, store_task_kernel_hist=False, verbose=5,
             verbose_indent=4, masks=None, cv_weights=1):
-        """Hyper-parameter optimisation with the reference's semantics (abstract_gp.py:152-306)."""
+        """Hyper-parameter optimisation with the reference's semantics (abstract_gp.py:152-306): on the device where
+        _device_fit_args says so (_fit_fused), else torch autograd with the caller's or the default optimizer
+        (_fit_generic)."""
         assert isinstance(loss_metric, str) and loss_metric.upper() in ["MLL", "GCV", "CV"]
-        assert self._nh > 0, "cannot fit without data"      # (self.n > 0).any() on the host mirror: no sync
+        assert self._has_data(), "cannot fit without data"
         assert isinstance(iterations, int) and iterations >= 0
+        assert optimizer is None or isinstance(optimizer, torch.optim.Optimizer)
         assert (isinstance(verbose, int) or isinstance(verbose, bool)) and verbose >= 0, \
             "require verbose is a non-negative int"
         assert isinstance(verbose_indent, int) and verbose_indent >= 0, \
@@ -736,65 +740,62 @@ class AbstractFastGP(torch.nn.Module):
         assert isinstance(stop_crit_wait_iterations, int) and stop_crit_wait_iterations > 0
         assert masks is None or isinstance(masks, torch.Tensor)
         loss_metric = loss_metric.upper()
-        hists = dict(loss=store_hists or store_loss_hist,
-                     scale=store_hists or (store_scale_hist and self.raw_scale.requires_grad),
-                     lengthscales=store_hists or (store_lengthscales_hist and self.raw_lengthscales.requires_grad),
-                     noise=store_hists or (store_noise_hist and self.raw_noise.requires_grad),
-                     task_kernel=store_hists or (store_task_kernel_hist and (
-                         self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad)))
+        hists = hist_flags(self, store_hists, store_loss_hist, store_scale_hist, store_lengthscales_hist,
+                           store_noise_hist, store_task_kernel_hist)
         stop = (np.log(1 + stop_crit_improvement_threshold), stop_crit_wait_iterations)
-        # wide inputs (d > 8): the device loop fgp_wide_fit_run only under FGP_WIDE_FIT_DEVICE=1 (default off: the
-        # generic autograd loop over fgp_wide_k1 / fgp_wide_k1_bwd)
-        wide_dev = (optimizer is None and loss_metric == "MLL" and self.d > _native.MAX_D
-                    and os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1" and self._wide_fit_ok())
-        if masks is not None and optimizer is None and loss_metric == "MLL" and (self._fused_ok() or wide_dev):
-            mk = self._masked_ysq(masks)
-            if mk is not None:
-                # only the outputs y[..., *masks] in the loss, shared hyper-parameters: the device fit on their
-                # Y = sum |ytilde_b|^2 with d_out = the selected count (abstract_gp.py:220-235, 253-260)
-                return self._fit_fused(iterations, 1e-1 if lr is None else lr, stop, hists, verbose, verbose_indent,
-                                       ysq=mk[0], d_out=mk[1])
-        fused = optimizer is None and masks is None and ((self._fused_ok() and (
-            loss_metric == "MLL" or self._alt_loss_ok(loss_metric, cv_weights))) or wide_dev)
+        dev = self._device_fit_args(loss_metric, optimizer, masks, cv_weights)
+        if dev is not None:
+            return self._fit_fused(iterations, 1e-1 if lr is None else lr, stop, hists, verbose, verbose_indent, **dev)
         if optimizer is None:
-            optimizer = None if fused else self.get_default_optimizer(lr)
-        else:
-            assert isinstance(optimizer, torch.optim.Optimizer)
-        if fused:
-            return self._fit_fused(iterations, 1e-1 if lr is None else lr, stop, hists, verbose, verbose_indent,
-                                   loss_metric=loss_metric, cv_weight=float(cv_weights) if loss_metric == "CV" else 1.0)
+            optimizer = self.get_default_optimizer(lr)
         return self._fit_generic(loss_metric, iterations, optimizer, stop, hists, verbose, verbose_indent, masks,
                                  cv_weights)
+
+    def _has_data(self):
+        return self._nh > 0                     # (self.n > 0).any() on the host mirror: no sync
+
+    def _device_fit_args(self, loss_metric, optimizer, masks, cv_weights):
+        """The keyword arguments of _fit_fused (ysq, d_out, loss_metric, cv_weight) when this fit runs on the device,
+        else None: the default optimizer; the MLL inside _fused_ok -- with masks, when one eigen-problem carries the
+        selected outputs (_masked_ysq) -- or, wide inputs (d > 8), inside _wide_fit_ok under FGP_WIDE_FIT_DEVICE=1
+        (default off: the generic autograd loop over fgp_wide_k1 / fgp_wide_k1_bwd); GCV / CV inside _alt_loss_ok."""
+        if optimizer is not None:
+            return None
+        mll = loss_metric == "MLL"
+        wide_dev = (mll and self.d > _native.MAX_D and os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1"
+                    and self._wide_fit_ok())
+        if masks is not None:
+            # only the outputs y[..., *masks] in the loss, shared hyper-parameters: the device fit on their
+            # Y = sum |ytilde_b|^2 with d_out = the selected count (abstract_gp.py:220-235, 253-260)
+            mk = self._masked_ysq(masks) if mll and (self._fused_ok() or wide_dev) else None
+            return None if mk is None else dict(ysq=mk[0], d_out=mk[1])
+        if wide_dev or (self._fused_ok() and (mll or self._alt_loss_ok(loss_metric, cv_weights))):
+            return dict(loss_metric=loss_metric, cv_weight=float(cv_weights) if loss_metric == "CV" else 1.0)
+        return None
+
+    def _fit_problem_batch(self):
+        """What _fused_ok and _wide_fit_ok share: exp transforms, a fixed unit task kernel and a problem batch, which is
+        returned (_problem_batch; None when any of them fails)."""
+        tfs = self._tfs
+        if tfs["scale"][1] is not _exp or tfs["lengthscales"][1] is not _exp or tfs["noise"][1] is not _exp:
+            return None
+        if self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad:
+            return None
+        if not self._task_unit():
+            return None
+        return self._problem_batch()
 
     def _fused_ok(self):
         # (the adaptive nugget of ONE task is the plain one: noise |tr_00 / tr_00| = noise, util.py:286-290 -- the
         # trace sqrt(n) sum_k lambda_k = n k1[0] > 0 for these positive kernels)
-        n = self._nh
-        if n < 16 or self.d > 8:
-            return False
-        if self._tfs["scale"][1] is not _exp or self._tfs["lengthscales"][1] is not _exp or \
-                self._tfs["noise"][1] is not _exp:
-            return False
-        if self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad:
-            return False
-        if not self._task_unit():
-            return False
-        pb = self._problem_batch()
-        return pb is not None
+        return self._nh >= 16 and self.d <= 8 and self._fit_problem_batch() is not None
 
     def _wide_fit_ok(self):
         """The wide device fit loop (fgp_wide_fit_run, wide_fit.WideMLL) applies: 9 <= d <= 64, n >= 16, exp transforms,
         a fixed unit task kernel and ONE eigen-problem (hyper-parameters shared by the outputs)."""
         if not (_native.MAX_D < self.d <= _native.WIDE_MAX_D) or self._nh < 16:
             return False
-        if self._tfs["scale"][1] is not _exp or self._tfs["lengthscales"][1] is not _exp or \
-                self._tfs["noise"][1] is not _exp:
-            return False
-        if self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad:
-            return False
-        if not self._task_unit():
-            return False
-        pb = self._problem_batch()
+        pb = self._fit_problem_batch()
         return pb is not None and pb[1] == 1
 
     def _wide_parts_key(self, n):
@@ -818,9 +819,7 @@ class AbstractFastGP(torch.nn.Module):
         return WideMLL(self._FAMILY, self._wide_fit_parts(n), self._ysq(pb_shape, G) if ysq is None else ysq,
                        self.raw_scale.detach().reshape(1), self.raw_lengthscales.detach().reshape(1, dl),
                        self.raw_noise.detach().reshape(1), logdet_weight=d_out / G, d_out=d_out,
-                       requires_grad=(self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad,
-                                      self.raw_noise.requires_grad),
-                       lr=lr, max_iters=min(iterations + 1, 8192))
+                       requires_grad=self._raw_requires_grad(), lr=lr, max_iters=min(iterations + 1, 8192))
 
     def _alt_loss_ok(self, loss_metric, cv_weights):
         """fit(loss_metric="GCV" / "CV") on the device (fgp_nll_desc.loss_metric, ABI 16): the spectral path
@@ -879,14 +878,8 @@ class AbstractFastGP(torch.nn.Module):
         yt = self.get_ytilde(0)
         return ops.sum_sq(yt.reshape(-1, yt.shape[-1]), G)
 
-    def _log_header(self, verbose, indent):
-        if verbose:
-            s = "%16s | %-10s | %-10s | %-10s" % ("iter of %.1e" % self._iters_for_log, "loss", "term1", "term2")
-            print(" " * indent + s)
-            print(" " * indent + "~" * len(s))
-
-    def _log_row(self, i, loss, t1, t2, indent):
-        print(" " * indent + "%16.2e | %-10.2e | %-10.2e | %-10.2e" % (i, loss, t1, t2))
+    def _raw_requires_grad(self):
+        return self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad, self.raw_noise.requires_grad
 
     def _fused_engine(self, iterations, lr, ysq=None, d_out=None, loss_metric="MLL", cv_weight=1.0):
         """The FusedMLL of this GP's fit: G eigen-problems from the part-product spectra, the regenerated
@@ -903,119 +896,50 @@ class AbstractFastGP(torch.nn.Module):
         gen = self._parts_gen(n) if basis is None else None
         parts = self._k1parts(n) if (gen is None and basis is None) else None
         ls_raw = self.raw_lengthscales.detach()
-        ls2 = ls_raw.reshape(-1, ls_raw.shape[-1])
+        s_raw, l_raw = self.raw_scale.detach().reshape(-1), ls_raw.reshape(-1, ls_raw.shape[-1])
+        nz_raw = self.raw_noise.detach().reshape(-1)
         max_iters = iterations + 1 if G == 1 and iterations < 8192 else min(iterations + 1, 64)
-        rg = (self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad, self.raw_noise.requires_grad)
+        w, const, rg = d_out / G, mll_constant(d_out, n), self._raw_requires_grad()
+        if ysq is None:
+            ysq = self._ysq(pb_shape, G)
         if basis is not None:
             # the spectral fit's engine, reused across fit() calls of this geometry (fit_engine.cached_engine)
-            return cached_engine(self._FAMILY, self._ysq(pb_shape, G) if ysq is None else ysq,
-                                 self.raw_scale.detach().reshape(-1), ls2, self.raw_noise.detach().reshape(-1),
-                                 logdet_weight=d_out / G, mll_const=mll_constant(d_out, n), requires_grad=rg, lr=lr,
-                                 max_iters=max_iters, basis=basis, loss_metric=loss_metric, cv_weight=cv_weight)
-        return FusedMLL(self._FAMILY, parts, self._ysq(pb_shape, G) if ysq is None else ysq,
-                        self.raw_scale.detach().reshape(-1), ls2,
-                        self.raw_noise.detach().reshape(-1), logdet_weight=d_out / G,
-                        mll_const=mll_constant(d_out, n),
-                        requires_grad=(self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad,
-                                       self.raw_noise.requires_grad),
-                        lr=lr, max_iters=max_iters, gen=gen, basis=basis, loss_metric=loss_metric, cv_weight=cv_weight)
+            return cached_engine(self._FAMILY, ysq, s_raw, l_raw, nz_raw, logdet_weight=w, mll_const=const,
+                                 requires_grad=rg, lr=lr, max_iters=max_iters, basis=basis, loss_metric=loss_metric,
+                                 cv_weight=cv_weight)
+        return FusedMLL(self._FAMILY, parts, ysq, s_raw, l_raw, nz_raw, logdet_weight=w, mll_const=const,
+                        requires_grad=rg, lr=lr, max_iters=max_iters, gen=gen, loss_metric=loss_metric,
+                        cv_weight=cv_weight)
 
     def _fit_fused(self, iterations, lr, stop, hists, verbose, indent, ysq=None, d_out=None, loss_metric="MLL",
                    cv_weight=1.0):
         """Device-resident fit (the engine of _fused_engine; the reference's loop semantics: loss history, early
         stopping, best iterate) of the MLL, or of the GCV / CV loss (abstract_gp.py:242-273, whose history holds
-        the loss itself where the MLL's holds -loss)."""
-        logtol, wait_max = stop
+        the loss itself where the MLL's holds -loss), by the one of fit_loop's four strategies that applies."""
         eng = (self._fused_engine(iterations, lr, ysq, d_out) if loss_metric == "MLL" else
                self._fused_engine(iterations, lr, ysq, d_out, loss_metric=loss_metric, cv_weight=cv_weight))
-        self._iters_for_log = iterations
-        self._log_header(verbose, indent)
-        best, save, waited = math.inf, math.inf, 0
-        best_i, i, i0, chunk = 0, 0, 0, 4
-        total = iterations + 1
-        done = False
-        losses = []
-        persist = getattr(eng, "persist_ok", lambda: False)()
-        if persist and not verbose and not any(hists.values()):
-            # the whole fit in one launch (fgp_fit_persist), which leaves the best iterate in the engine's raw
-            # parameters (ABI 18): they are restored while the launch runs, and the control word is read after
-            # that (the host work overlaps the fit instead of following it)
-            ip = eng.run_persist(iterations, logtol, wait_max, defer=True)
-            if ip is not None:
-                self._restore_best(eng, eng.raw)
-                if ip < 0:
-                    ip = eng.persist_result()
-                if ip is not None:
-                    eng.release_inputs()
-                    return {"iterations": ip}
-            persist = False       # a barrier give-up restored the entry state: the launch per iteration below
-        if persist:
-            # the whole fit in one launch (fgp_fit_persist: the early-stopping rule on the device); the last
-            # iteration and the failure word are read back.  A barrier give-up (None) restored the entry state:
-            # the fit then runs below on the launch per iteration (the same trajectory bit for bit).
-            no_stop = wait_max > iterations
-            ip = eng.run_persist(iterations, logtol, wait_max)
-            if ip is not None:
-                i = ip
-                done = True
-                if no_stop:
-                    l0 = eng.loss_hist[:total, 0, 0]
-                    best_i = torch.where(torch.isnan(l0), torch.full_like(l0, math.inf), l0).argmin()
-                if not no_stop or verbose or hists["loss"]:
-                    rows = eng.loss_hist[:i + 1, 0].cpu().tolist()
-                    for r, row in enumerate(rows):
-                        lv = float(row[0])
-                        losses.append((lv, float(row[1]), float(row[2])))
-                        if lv < best and not no_stop:
-                            best, best_i = lv, r
-                        if verbose and (r % verbose == 0 or r == i):
-                            self._log_row(r, lv, row[1], row[2], indent)
-        if not done and wait_max > iterations:
-            # no early stop is possible: every iteration runs, the best iterate is the first minimum of
-            # the loss history (the host rule `lv < best`; NaN never best), found on the device -- one
-            # enqueue, no host sync unless losses are logged or returned
-            eng.run(0, total, final_no_update=True)
-            lh_dev = eng.loss_hist[:total, 0]
-            l0 = lh_dev[:, 0]
-            best_i = torch.where(torch.isnan(l0), torch.full_like(l0, math.inf), l0).argmin()
-            i = iterations
-            done = True
-            if verbose or hists["loss"]:
-                losses = [tuple(r) for r in lh_dev.cpu().tolist()]
-                for r in range(total):
-                    if verbose and (r % verbose == 0 or r == iterations):
-                        self._log_row(r, losses[r][0], losses[r][1], losses[r][2], indent)
-        while not done:
-            k = min(chunk, total - i0)
-            eng.run(i0, k, final_no_update=(i0 + k == total))
-            lh = eng.loss_hist[i0:i0 + k, 0].cpu()
-            for r in range(k):
-                i = i0 + r
-                lv = float(lh[r, 0])
-                losses.append((lv, float(lh[r, 1]), float(lh[r, 2])))
-                if lv < best:
-                    best, best_i = lv, i
-                if (save - lv) > logtol:
-                    waited = 0
-                    save = best
-                else:
-                    waited += 1
-                brk = i == iterations or waited == wait_max
-                if verbose and (i % verbose == 0 or brk):
-                    self._log_row(i, lv, losses[-1][1], losses[-1][2], indent)
-                if brk:
-                    done = True
-                    break
-            i0 += k
-            chunk = min(64, chunk * 2)
+        # the whole fit in one launch where the engine can; None after a barrier give-up: the launch per iteration
+        single = eng.persist_ok()
+        quiet = single and not verbose and not any(hists.values())
+        out = fit_persist_deferred(eng, iterations, *stop, self._restore_best) if quiet else None
+        if out is None:
+            rule, log = StopRule(iterations, *stop), FitLog(verbose, indent, iterations)
+            if single and not quiet:
+                out = fit_persist(eng, rule, log, hists["loss"])
+            if out is None:
+                out = (fit_chunked(eng, rule, log) if rule.can_stop_early else
+                       fit_all_rows(eng, rule, log, hists["loss"]))
+        i, best_i, losses = out
+        data = {"iterations": i}
+        if best_i is None:                    # (the deferred single launch: the best iterate is restored already)
+            eng.release_inputs()
+            return data
         raw_hist = eng.raw_hist[:i + 1]
         s_raw, l_raw, nz_raw = eng.split_raw(raw_hist)
         # (a device index tensor: index_select, not raw_hist[t] -- a 0-d index tensor is read back to the host)
         best_row = raw_hist.index_select(0, best_i.reshape(1))[0] if torch.is_tensor(best_i) else raw_hist[best_i]
         self._restore_best(eng, best_row)
-        if hasattr(eng, "release_inputs"):
-            eng.release_inputs()
-        data = {"iterations": i}
+        eng.release_inputs()
         if hists["loss"]:
             sgn = -1.0 if loss_metric == "MLL" else 1.0        # metric_val: -loss (MLL), loss (GCV, CV)
             data["loss_hist"] = torch.tensor([sgn * v[0] for v in losses])
@@ -1026,7 +950,7 @@ class AbstractFastGP(torch.nn.Module):
         if hists["noise"]:
             data["noise_hist"] = self.tf_noise(nz_raw.reshape((-1,) + self.raw_noise.shape)).cpu()
         if hists["task_kernel"]:
-            tkr = eng.task_kernel_rows(raw_hist) if hasattr(eng, "task_kernel_rows") else None
+            tkr = eng.task_kernel_rows(raw_hist)
             if tkr is not None:
                 data["task_kernel_hist"] = tkr.detach().cpu()
             else:
@@ -1039,7 +963,7 @@ class AbstractFastGP(torch.nn.Module):
         (abstract_gp.py:285-296), the hyper-parameter-dependent caches dropped."""
         b_s, b_l, b_n = eng.split_raw(best_row)
         restore = [("raw_scale", b_s), ("raw_lengthscales", b_l), ("raw_noise", b_n)]
-        tsk = eng.split_task(best_row) if hasattr(eng, "split_task") else None
+        tsk = eng.split_task(best_row)
         if tsk is not None:                             # a multitask engine that also learns the task kernel
             b_f, b_v = tsk
             restore += [("raw_factor_task_kernel", b_f), ("raw_noise_task_kernel", b_v)]
@@ -1051,7 +975,35 @@ class AbstractFastGP(torch.nn.Module):
         self._cache = {k: v for k, v in self._cache.items() if not k[2]}    # keep data-only entries (ytilde, spectra)
         self._snap = None
 
+    def _mll_of(self, norm, logdet, masks, d_out, n):
+        """(loss, term1, term2, None) of the MLL from the norm and logdet terms [..., 1] of the outputs / the
+        eigen-problems (abstract_gp.py:252-261), n the number of observations of one output."""
+        if masks is None:
+            t1 = norm.sum()
+            t2 = d_out / torch.tensor(logdet.shape).prod() * logdet.sum()
+        else:
+            t1 = norm[(..., *masks, 0)].sum()
+            t2 = logdet.expand(list(self.shape_batch) + [1])[(..., *masks, 0)].sum()
+        return 0.5 * (t1 + t2 + d_out * n * np.log(2 * np.pi)), t1, t2, None
+
+    def _gcv_of(self, numer, denom, masks):
+        """(loss, numer, denom, metric) of the GCV loss (abstract_gp.py:242-251)."""
+        if masks is None:
+            t1, t2 = numer, denom
+        else:
+            t1 = numer[(..., *masks, slice(None))]
+            t2 = denom.expand(list(self.shape_batch) + [1])[(..., *masks, slice(None))]
+        loss = (t1 / t2).sum()
+        return loss, t1, t2, loss
+
+    def _cv_of(self, sq, masks):
+        """(loss, nan, nan, metric) of the CV loss from the outputs' weighted squares [..., 1] (abstract_gp.py:262-273)."""
+        loss = sq.sum() if masks is None else sq[(..., *masks, 0)].sum()
+        nan = torch.nan * torch.ones(1)
+        return loss, nan, nan, loss
+
     def _loss_generic(self, loss_metric, masks, cv_weights, d_out):
+        """(loss, term1, term2, metric) through torch autograd; metric None: the history holds -loss (the MLL)."""
         n = self._nh
         A, logdet = self.get_inv_log_det(n)
         A = A[..., 0, 0, :]
@@ -1059,61 +1011,38 @@ class AbstractFastGP(torch.nn.Module):
         if loss_metric == "MLL":
             z = yt * A
             norm = (yt.conj() * z).real.sum(-1, keepdim=True) if yt.is_complex() else (yt * z).sum(-1, keepdim=True)
-            logdet = logdet[..., None]
-            if masks is None:
-                t1 = norm.sum()
-                t2 = d_out / torch.tensor(logdet.shape).prod() * logdet.sum()
-            else:
-                t1 = norm[(..., *masks, 0)].sum()
-                t2 = logdet.expand(list(self.shape_batch) + [1])[(..., *masks, 0)].sum()
-            return 0.5 * (t1 + t2 + d_out * n * np.log(2 * np.pi)), t1, t2, None
+            return self._mll_of(norm, logdet[..., None], masks, d_out, n)
         if loss_metric == "GCV":
             z = yt * A
             numer = (z.conj() * z).real.sum(-1, keepdim=True) if z.is_complex() else (z * z).sum(-1, keepdim=True)
             denom = ((A.real if A.is_complex() else A).sum(-1, keepdim=True) / n) ** 2
-            if masks is None:
-                t1, t2 = numer, denom
-            else:
-                t1 = numer[(..., *masks, slice(None))]
-                t2 = denom.expand(list(self.shape_batch) + [1])[(..., *masks, slice(None))]
-            loss = (t1 / t2).sum()
-            return loss, t1, t2, loss
-        # CV (util.py:381-385 single task; abstract_gp.py:262-273)
+            return self._gcv_of(numer, denom, masks)
+        # CV (util.py:381-385 single task)
         coeffs = self._solve(self._y[0], n)
         lam = self.get_lam(0, 0, n)
         inv_diag = (1 / (lam * np.sqrt(n))).mean(-1, keepdim=True)
         sq = ((coeffs / inv_diag) ** 2 * cv_weights)
-        sq = (sq.real if sq.is_complex() else sq).sum(-1, keepdim=True)
-        loss = sq.sum() if masks is None else sq[(..., *masks, 0)].sum()
-        nan = torch.nan * torch.ones(1)
-        return loss, nan, nan, loss
+        return self._cv_of((sq.real if sq.is_complex() else sq).sum(-1, keepdim=True), masks)
 
     def _fit_generic(self, loss_metric, iterations, optimizer, stop, hists, verbose, indent, masks, cv_weights):
-        logtol, wait_max = stop
+        """The autograd loop over _loss_generic with a torch optimizer, the reference's own (abstract_gp.py:236-306)."""
         if masks is not None:
             masks = torch.atleast_2d(masks)
             assert masks.ndim == 2 and len(masks) <= len(self.shape_batch)
             d_out = torch.empty(self.shape_batch)[(..., *masks)].numel()
         else:
             d_out = int(torch.tensor(self.shape_batch).prod())
-        self._iters_for_log = iterations
-        self._log_header(verbose, indent)
+        rule = StopRule(iterations, *stop)
+        log = FitLog(verbose, indent, iterations)
         rec = {k: [] for k in ("loss", "scale", "lengthscales", "noise", "task_kernel")}
-        best, save, waited = math.inf, math.inf, 0
         best_params = None
         for i in range(iterations + 1):
             self._cache = {k: v for k, v in self._cache.items() if not k[2]}
             loss, t1, t2, metric = self._loss_generic(loss_metric, masks, cv_weights, d_out)
             lv = loss.item()
-            if lv < best:
-                best = lv
+            if lv < rule.best:
                 best_params = {k: p.data.clone() for k, p in self.named_parameters()}
-            if (save - lv) > logtol:
-                waited = 0
-                save = best
-            else:
-                waited += 1
-            brk = i == iterations or waited == wait_max
+            brk = rule.push(i, lv)
             if hists["loss"]:
                 rec["loss"].append(-lv if metric is None else metric.item())
             if hists["scale"]:
@@ -1124,9 +1053,7 @@ class AbstractFastGP(torch.nn.Module):
                 rec["noise"].append(self.noise.detach().cpu())
             if hists["task_kernel"]:
                 rec["task_kernel"].append(self.gram_matrix_tasks.detach().cpu())
-            if verbose and (i % verbose == 0 or brk):
-                self._log_row(i, lv, t1.item() if t1.numel() == 1 else torch.nan,
-                              t2.item() if t2.numel() == 1 else torch.nan, indent)
+            log.row(i, lv, t1, t2, brk)
             if brk:
                 break
             loss.backward()
@@ -1143,6 +1070,7 @@ class AbstractFastGP(torch.nn.Module):
             if hists[k]:
                 data[k + "_hist"] = torch.stack(rec[k])
         return data
+
 
     # ------------------------------------------------------------------ prediction
     def _hyp_rows(self, batch_params):

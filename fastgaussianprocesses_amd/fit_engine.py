@@ -152,7 +152,64 @@ def spec_basis_gen(gen, n, device, force=False):
     return out
 
 
-class FusedMLL(object):
+class FitEngine(object):
+    """What the fit drivers (fit_loop's four strategies, batch._fit_loop, AbstractFastGP._fit_fused / _restore_best) use
+    of a device-resident fit: `device`, `n_params`, `raw` [n_params] (the current raw parameters), `sizes` (the
+    lengths of raw's leading scale, lengthscales and noise blocks), the histories `loss_hist` [rows, _hist_problems(),
+    3] and `raw_hist` [rows, n_params] with `max_iters` rows, and run().  A subclass sets those, gives run() and the two
+    history hooks, and overrides the defaults below where it has more to offer."""
+
+    max_iters = 0
+    loss_hist = raw_hist = None
+
+    def run(self, iter0, iters, final_no_update=False):
+        """Enqueue `iters` fit iterations writing history rows iter0 .. iter0 + iters - 1 on the current stream, without
+        host synchronisation; with final_no_update the last of them only evaluates (the fit's last iteration)."""
+        raise NotImplementedError
+
+    def _hist_problems(self):
+        """Loss rows per iteration: the engine's independent problems, or 1 (one loss over all of them)."""
+        return 1
+
+    def _history_moved(self):
+        """The histories were reallocated: point the engine's descriptor at loss_hist / raw_hist."""
+        raise NotImplementedError
+
+    def ensure_history(self, iters):
+        """Room for `iters` history rows: max(iters, twice the old size, 16), zero-filled, the old rows kept."""
+        if iters <= self.max_iters:
+            return
+        new_max = max(iters, 2 * self.max_iters, 16)
+        lh = torch.zeros((new_max, self._hist_problems(), 3), dtype=torch.float64, device=self.device)
+        rh = torch.zeros((new_max, self.n_params), dtype=torch.float64, device=self.device)
+        if self.loss_hist is not None:
+            lh[:self.max_iters] = self.loss_hist
+            rh[:self.max_iters] = self.raw_hist
+        self.loss_hist, self.raw_hist, self.max_iters = lh, rh, new_max
+        self._history_moved()
+
+    def split_raw(self, raw_vec):
+        """(raw scale, raw lengthscales, raw noise) of a raw vector or of history rows."""
+        S, L, Nn = self.sizes[:3]
+        return raw_vec[..., :S], raw_vec[..., S:S + L], raw_vec[..., S + L:S + L + Nn]
+
+    def persist_ok(self):
+        """The engine can run the whole fit in one launch (run_persist / persist_result)."""
+        return False
+
+    def release_inputs(self):
+        """Drop the references to the caller's inputs once the fit is enqueued (an engine that outlives its fit)."""
+
+    def split_task(self, raw_vec):
+        """(raw task factor, raw task noise) of an engine that learns the task kernel, else None."""
+        return None
+
+    def task_kernel_rows(self, raw_rows):
+        """The task kernel of every history row of an engine that learns it, else None."""
+        return None
+
+
+class FusedMLL(FitEngine):
     def __init__(self, family, parts, ysq, raw_scale, raw_lengthscales, raw_noise, logdet_weight, mll_const,
                  requires_grad=(True, True, False), lr=0.1, max_iters=1, parts_per_problem=False, per_problem=None,
                  gen=None, basis=None, mt=None, loss_metric="MLL", cv_weight=1.0):
@@ -172,6 +229,12 @@ class FusedMLL(object):
                 multitask: GCV ABI 17, CV ABI 18; cv_weight the scalar cv_weights of AbstractGP.fit); their loss
                 history holds [loss, numer, denom] (CV: [loss, nan, nan])
         """
+        # set later, by the call that first needs each: the graph token (_graph_token), the single launch's workgroups
+        # (persist_workgroups), a captured / a pending launch's control word (run_persist), its entry state and the
+        # Rprop reset of a reused engine (refill), the problem groups' descriptors and streams (_group_descs)
+        self._token = self._persist_wg = self._ctrl = self._pending = self._raw_entry = self._rprop_init = None
+        self._groups_key = self._groups = self._streams = None
+        self.persist_failures = 0
         if loss_metric != "MLL" and basis is None and mt is None:
             raise ValueError("GCV / CV fits run on the spectral path only (basis, or the multitask spectra)")
         require_device(ysq, "FusedMLL")
@@ -233,8 +296,8 @@ class FusedMLL(object):
         # Rprop state (previous gradient, step sizes), the gradient and the loss / parameter histories in ONE
         # zeroed allocation (one fill kernel + the step sizes' fill: a graph-replayed small fit pays per node)
         self.per_problem = bool(G == 1 if per_problem is None else per_problem)
-        hmax = max(int(max_iters), 16)                  # ensure_history's first size
-        hg = self.G if self.per_problem else 1
+        hmax = max(int(max_iters), 16)                  # ensure_history's first size; it only grows them from here
+        hg = self._hist_problems()
         np_ = self.n_params
         blob = torch.zeros((3 * np_ + hmax * hg * 3 + hmax * np_,), dtype=torch.float64, device=self.device)
         st = blob[:3 * np_].view(3, np_)
@@ -244,7 +307,6 @@ class FusedMLL(object):
         self.loss_hist = blob[3 * np_:3 * np_ + hmax * hg * 3].view(hmax, hg, 3)
         self.raw_hist = blob[3 * np_ + hmax * hg * 3:].view(hmax, np_)
         self.max_iters = hmax
-        self._init_max_iters = max_iters
         self._nll = N.NllDesc(
             family=self.family, log2n=self.m, d=self.d, G=self.G,
             parts=(self.parts.data_ptr() if self.parts is not None else 0),
@@ -295,25 +357,12 @@ class FusedMLL(object):
         self._nll.partials = self.partials.data_ptr()
         self.requires_grad = tuple(int(bool(r)) for r in requires_grad)
         self.mll_const = float(mll_const)
-        self._fit = None
-        self._refresh_fit_desc()
-        self.ensure_history(self._init_max_iters)
+        self._history_moved()
 
-    def ensure_history(self, iters):
-        if iters <= self.max_iters:
-            return
-        new_max = max(iters, 2 * self.max_iters, 16)
-        lh = torch.zeros((new_max, self.G if self.per_problem else 1, 3), dtype=torch.float64, device=self.device)
-        rh = torch.zeros((new_max, self.n_params), dtype=torch.float64, device=self.device)
-        if self.loss_hist is not None:
-            lh[:self.max_iters] = self.loss_hist
-            rh[:self.max_iters] = self.raw_hist
-        self.loss_hist, self.raw_hist, self.max_iters = lh, rh, new_max
-        self._refresh_fit_desc()
+    def _hist_problems(self):
+        return self.G if self.per_problem else 1
 
-    def _refresh_fit_desc(self):
-        if not hasattr(self, "mll_const"):
-            return
+    def _history_moved(self):
         self._fit = N.FitDesc(
             n_params=self.n_params, raw=self.raw.data_ptr(), rprop_prev=self.prev.data_ptr(),
             rprop_step=self.step.data_ptr(), grad_out=self.grad.data_ptr(), loss_hist=self.loss_hist.data_ptr(),
@@ -383,7 +432,7 @@ class FusedMLL(object):
         # run_persist's entry state (a barrier give-up restores it): the caller's tensors themselves, not a copy (the
         # fit replaces a GP's Parameters by new ones, abstract_gp.py:295-296, it never writes into them)
         self._raw_entry = src
-        init = getattr(self, "_rprop_init", None)      # [[0 ...], [lr ...]] on the device, kept per lr
+        init = self._rprop_init                        # [[0 ...], [lr ...]] on the device, kept per lr
         if init is None or init[0] != float(lr):
             t = torch.zeros_like(self._rprop_state)
             t[1].fill_(float(lr))
@@ -398,7 +447,7 @@ class FusedMLL(object):
 
     def _graph_token(self):
         """This engine's token for fgp_fit_run_graph's cache (released when the engine is freed)."""
-        tok = getattr(self, "_token", None)
+        tok = self._token
         if tok is None:
             global _NEXT_TOKEN
             _NEXT_TOKEN += 1
@@ -406,7 +455,7 @@ class FusedMLL(object):
         return tok
 
     def __del__(self):
-        tok = getattr(self, "_token", None)
+        tok = self._token
         if tok is not None:
             try:
                 N.call("fgp_fit_graph_release", tok)
@@ -423,7 +472,7 @@ class FusedMLL(object):
         all be co-resident on this device)."""
         if os.environ.get("FGP_FIT_PERSIST", "1")[:1] == "0" or self.G != 1 or not self._nll.basis:
             return 0
-        wg = getattr(self, "_persist_wg", None)      # (a function of the engine's geometry and the device only)
+        wg = self._persist_wg                        # (a function of the engine's geometry and the device only)
         if wg is None:
             ok = ctypes.c_int(0)
             N.call("fgp_fit_persist_ok", self._nll, ctypes.byref(ok))
@@ -446,7 +495,7 @@ class FusedMLL(object):
         self.ensure_history(iterations + 1)
         ctrl = torch.empty((4,), dtype=torch.int32, device=self.device)   # (the launch clears the words it reports)
         capturing = torch.cuda.is_current_stream_capturing()
-        entry, self._raw_entry = getattr(self, "_raw_entry", None), None
+        entry, self._raw_entry = self._raw_entry, None
         raw0 = None if capturing else (entry if entry is not None else self.raw.clone())
         N.call("fgp_fit_persist", self._nll, self._fit, int(iterations), float(logtol), int(wait_max),
                ctrl.data_ptr(), self.stream())
@@ -467,13 +516,13 @@ class FusedMLL(object):
                 torch.cat(raw0, out=self.raw)
             else:
                 self.raw.copy_(raw0)
-            self.persist_failures = getattr(self, "persist_failures", 0) + 1
+            self.persist_failures += 1
             return None
         return int(c[1])
 
     def check_persist(self):
         """Raise for a failed fgp_fit_persist whose control word could not be read when it ran (a capture)."""
-        ctrl = getattr(self, "_ctrl", None)
+        ctrl = self._ctrl
         if ctrl is None:
             return None
         self._ctrl = None
@@ -498,9 +547,9 @@ class FusedMLL(object):
     def _group_descs(self, groups):
         """(nll, fit, partials) sub-descriptors of problem ranges [G k / groups, G (k+1) / groups)."""
         key = (groups, self._fit.loss_hist, self._fit.raw_hist)
-        if getattr(self, "_groups_key", None) == key:
+        if self._groups_key == key:
             return self._groups
-        if getattr(self, "_streams", None) is None or len(self._streams) < groups:
+        if self._streams is None or len(self._streams) < groups:
             self._streams = [torch.cuda.Stream(self.device) for _ in range(groups)]
         G, n, d = self.G, self.n, self.d
         out = []
@@ -562,10 +611,6 @@ class FusedMLL(object):
     def stage(self, k):
         """Enqueue one kernel of the fwd/bwd pipeline (fgp_nll_stage; per-kernel timing)."""
         N.call("fgp_nll_stage", self._nll, int(k), self.stream())
-
-    def split_raw(self, raw_vec):
-        S, L, Nn = self.sizes
-        return raw_vec[..., :S], raw_vec[..., S:S + L], raw_vec[..., S + L:S + L + Nn]
 
     def split_task(self, raw_vec):
         """(raw task factor [.., T R], raw task noise [.., T]) of a learned task kernel's raw vector(s); None without."""

@@ -29,7 +29,7 @@ import torch
 from . import ops
 from . import _native as N
 from .fast_gp import _IDENTITY_TFS, AbstractFastGP, _Hyper, _as_size, _exp, _identity
-from .fit_engine import RPROP_ETAS, RPROP_STEPS, FusedMLL, mll_constant
+from .fit_engine import RPROP_ETAS, RPROP_STEPS, FitEngine, FusedMLL, mll_constant
 
 
 def _to_n_tensor(n):
@@ -339,18 +339,25 @@ class MultiTaskFastGP(AbstractFastGP):
         include/fgp_hip.h mt_tasks) covers: every task with the same n >= 16, at most 8 tasks, d <= 6, no
         parameter batch, the task kernel fixed (derivative-informed GPs fix it at 1, abstract_gp.py:146-150),
         exp parameter transforms, no adaptive nugget.  FGP_MT_FUSED=0 takes the generic autograd loop."""
-        if os.environ.get("FGP_MT_FUSED", "1")[:1] == "0" or os.environ.get("FGP_MT_GENERAL", "0")[:1] == "1":
+        if os.environ.get("FGP_MT_GENERAL", "0")[:1] == "1":
+            return False
+        if self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad:
+            return False
+        return self._mt_equal_n_ok()
+
+    def _mt_equal_n_ok(self):
+        """What _mt_fused_ok and _mt_learn_ok share: FGP_MT_FUSED not 0, every task with the same n >= 16, at most 8
+        tasks, d <= 6, no adaptive nugget, no batch, exp transforms, pair spectra within MT_SPECTRA_CAP bytes."""
+        if os.environ.get("FGP_MT_FUSED", "1")[:1] == "0":
             return False
         ns = self._ns
-        n = ns[0]
-        if not (n >= 16 and all(v == n for v in ns) and self.num_tasks <= 8 and self.d <= 6):
+        n, T = ns[0], self.num_tasks
+        if not (n >= 16 and all(v == n for v in ns) and T <= 8 and self.d <= 6):
             return False
-        if self.adaptive_nugget or len(self.shape_batch) or self.raw_factor_task_kernel.requires_grad or \
-                self.raw_noise_task_kernel.requires_grad:
+        if self.adaptive_nugget or len(self.shape_batch):
             return False
         if any(self._tfs[k][1] is not _exp for k in ("scale", "lengthscales", "noise")):
             return False
-        T = self.num_tasks
         if (T * (T + 1) // 2) * (1 << self.d) * n * 16 > MT_SPECTRA_CAP:
             return False
         return tuple(self.raw_scale.shape) == (1,) and tuple(self.raw_noise.shape) == (1,) and \
@@ -361,26 +368,14 @@ class MultiTaskFastGP(AbstractFastGP):
         variants + k_mt_learn_step; the reference's default for num_tasks > 1, abstract_gp.py:116-139): _mt_fused_ok's
         domain except the fixed task kernel -- the factor [T, R] with the identity transform, the task noise [T] with the
         exp or the identity transform, no parameter batch."""
-        if os.environ.get("FGP_MT_FUSED", "1")[:1] == "0":
-            return False
         if not (self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad):
             return False
-        ns = self._ns
-        n, T = ns[0], self.num_tasks
-        if not (n >= 16 and all(v == n for v in ns) and 2 <= T <= 8 and self.d <= 6):
-            return False
-        if self.adaptive_nugget or len(self.shape_batch):
-            return False
-        if any(self._tfs[k][1] is not _exp for k in ("scale", "lengthscales", "noise")):
-            return False
-        if self.tf_factor_task_kernel is not _identity or self.tf_noise_task_kernel not in (_exp, _identity):
+        T = self.num_tasks
+        if T < 2 or self.tf_factor_task_kernel is not _identity or self.tf_noise_task_kernel not in (_exp, _identity):
             return False
         if tuple(self.raw_factor_task_kernel.shape[:-1]) != (T,) or tuple(self.raw_noise_task_kernel.shape) != (T,):
             return False
-        if (T * (T + 1) // 2) * (1 << self.d) * n * 16 > MT_SPECTRA_CAP:
-            return False
-        return tuple(self.raw_scale.shape) == (1,) and tuple(self.raw_noise.shape) == (1,) and \
-            tuple(self.raw_lengthscales.shape) in ((1,), (self.d,))
+        return self._mt_equal_n_ok()
 
     def _mt_param_rows(self):
         """Parameter batches (docs/examples/batch_multitask/fgp_lattice.ipynb cell 6; abstract_gp.py:73-139: each
@@ -531,9 +526,7 @@ class MultiTaskFastGP(AbstractFastGP):
                               vexp=self.tf_noise_task_kernel is _exp)
         return FusedMLL(self._FAMILY, None, torch.zeros((1, n), device=self.device),
                         self.raw_scale.detach().reshape(-1), ls.reshape(1, -1), self.raw_noise.detach().reshape(-1),
-                        logdet_weight=1.0, mll_const=mll_constant(1, T * n),
-                        requires_grad=(self.raw_scale.requires_grad, self.raw_lengthscales.requires_grad,
-                                       self.raw_noise.requires_grad),
+                        logdet_weight=1.0, mll_const=mll_constant(1, T * n), requires_grad=self._raw_requires_grad(),
                         lr=lr, max_iters=min(iterations + 1, 64), loss_metric=loss_metric, cv_weight=cv_weight, mt=mt)
 
     # ------------------------------------------------------------------ kernel parts and kernels
@@ -783,147 +776,36 @@ class MultiTaskFastGP(AbstractFastGP):
         idx = torch.arange(nsum, device=self.device)
         return kinv[..., idx, idx]
 
-    def fit(self, loss_metric="MLL", iterations=5000, lr=None, optimizer=None, stop_crit_improvement_threshold=5e-2,
-            stop_crit_wait_iterations=10, store_hists=False, store_loss_hist=False, store_scale_hist=False,
-            store_lengthscales_hist=False, store_noise_hist=False, store_task_kernel_hist=False, verbose=5,
-            verbose_indent=4, masks=None, cv_weights=1):
-        """abstract_gp.py:152-306 (every iteration recomputes the caches: FASTGP_FORCE_RECOMPILE)."""
-        assert isinstance(loss_metric, str) and loss_metric.upper() in ["MLL", "GCV", "CV"]
-        assert sum(self._ns) > 0, "cannot fit without data"
-        assert isinstance(iterations, int) and iterations >= 0
-        default_optimizer = optimizer is None
-        if optimizer is None:
-            optimizer = self.get_default_optimizer(lr)
-        assert isinstance(optimizer, torch.optim.Optimizer)
-        assert (isinstance(verbose, int) or isinstance(verbose, bool)) and verbose >= 0, \
-            "require verbose is a non-negative int"
-        assert isinstance(verbose_indent, int) and verbose_indent >= 0, \
-            "require verbose_indent is a non-negative int"
-        assert np.isscalar(stop_crit_improvement_threshold) and 0 < stop_crit_improvement_threshold, \
-            "require stop_crit_improvement_threshold is a positive float"
-        assert isinstance(stop_crit_wait_iterations, int) and stop_crit_wait_iterations > 0
-        assert masks is None or isinstance(masks, torch.Tensor)
-        loss_metric = loss_metric.upper()
-        alt_dev = (loss_metric in ("GCV", "CV") and default_optimizer and masks is None and
-                   (self._mt_fused_ok() or self._mt_learn_ok()) and os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0")
+    # (fit, _fit_fused, _fit_generic: AbstractFastGP, over the three hooks below)
+    def _has_data(self):
+        return sum(self._ns) > 0
+
+    def _device_fit_args(self, loss_metric, optimizer, masks, cv_weights):
+        """The MLL on the device inside _mt_fused_ok or _mt_general_ok; GCV / CV of T tasks with equal n and a fixed or
+        a learned task kernel (k_mt_spec_iter's GCV / CV variants + k_spec_loss_step, ABI 17 / 18; util.py:371-394,
+        abstract_gp.py:242-272) unless FGP_ALT_LOSS_DEVICE=0."""
+        if optimizer is not None or masks is not None:
+            return None
+        if loss_metric == "MLL":
+            return {} if self._mt_fused_ok() or self._mt_general_ok() else None
+        ok = (self._mt_fused_ok() or self._mt_learn_ok()) and os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
         if loss_metric == "CV":
             # (one task: the reference's inv_diag is the single-task formula without the noise, util.py:383-386; a
             # per-point cv_weights needs the points' coefficients, not their Parseval sum)
-            alt_dev = alt_dev and self.num_tasks > 1 and (
+            ok = ok and self.num_tasks > 1 and (
                 np.isscalar(cv_weights) or (torch.is_tensor(cv_weights) and cv_weights.numel() == 1))
-        if alt_dev:
-            # GCV / CV of T tasks with equal n and a fixed task kernel (derivative-informed GPs) on the device:
-            # k_mt_spec_iter's GCV / CV variants + k_spec_loss_step (ABI 17 / 18; util.py:371-394,
-            # abstract_gp.py:242-272)
-            hists = dict(loss=store_hists or store_loss_hist,
-                         scale=store_hists or (store_scale_hist and self.raw_scale.requires_grad),
-                         lengthscales=store_hists or (store_lengthscales_hist and self.raw_lengthscales.requires_grad),
-                         noise=store_hists or (store_noise_hist and self.raw_noise.requires_grad),
-                         task_kernel=store_hists or (store_task_kernel_hist and (
-                             self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad)))
-            return self._fit_fused(iterations, 1e-1 if lr is None else lr,
-                                   (np.log(1 + stop_crit_improvement_threshold), stop_crit_wait_iterations), hists,
-                                   verbose, verbose_indent, loss_metric=loss_metric,
-                                   cv_weight=float(cv_weights) if loss_metric == "CV" else 1.0)
-        if loss_metric == "MLL" and default_optimizer and masks is None and (self._mt_fused_ok() or
-                                                                            self._mt_general_ok()):
-            learned_tk = self.raw_factor_task_kernel.requires_grad or self.raw_noise_task_kernel.requires_grad
-            hists = dict(loss=store_hists or store_loss_hist,
-                         scale=store_hists or (store_scale_hist and self.raw_scale.requires_grad),
-                         lengthscales=store_hists or (store_lengthscales_hist and self.raw_lengthscales.requires_grad),
-                         noise=store_hists or (store_noise_hist and self.raw_noise.requires_grad),
-                         task_kernel=store_hists or (store_task_kernel_hist and learned_tk))
-            return self._fit_fused(iterations, 1e-1 if lr is None else lr,
-                                   (np.log(1 + stop_crit_improvement_threshold), stop_crit_wait_iterations), hists,
-                                   verbose, verbose_indent)
-        logtol = np.log(1 + stop_crit_improvement_threshold)
-        h_loss = store_hists or store_loss_hist
-        h_scale = store_hists or (store_scale_hist and self.raw_scale.requires_grad)
-        h_ls = store_hists or (store_lengthscales_hist and self.raw_lengthscales.requires_grad)
-        h_noise = store_hists or (store_noise_hist and self.raw_noise.requires_grad)
-        h_tk = store_hists or (store_task_kernel_hist and (self.raw_factor_task_kernel.requires_grad or
-                                                           self.raw_noise_task_kernel.requires_grad))
-        if masks is not None:
-            masks = torch.atleast_2d(masks)
-            assert masks.ndim == 2 and len(masks) <= len(self.shape_batch)
-            d_out = torch.empty(self.shape_batch)[(..., *masks)].numel()
-        else:
-            d_out = int(torch.tensor(self.shape_batch).prod())
-        if verbose:
-            s = "%16s | %-10s | %-10s | %-10s" % ("iter of %.1e" % iterations, "loss", "term1", "term2")
-            print(" " * verbose_indent + s)
-            print(" " * verbose_indent + "~" * len(s))
-        mll_const = d_out * sum(self._ns) * np.log(2 * np.pi)
-        best, save, waited = math.inf, math.inf, 0
-        best_params = None
-        rec = {k: [] for k in ("loss", "scale", "lengthscales", "noise", "task_kernel")}
-        for i in range(iterations + 1):
-            self._cache = {k: v for k, v in self._cache.items() if not k[2]}
-            if loss_metric == "GCV":
-                numer, denom = self._gcv_numer_denom()
-                if masks is None:
-                    t1, t2 = numer, denom
-                else:
-                    t1 = numer[(..., *masks, slice(None))]
-                    t2 = denom.expand(list(self.shape_batch) + [1])[(..., *masks, slice(None))]
-                loss = (t1 / t2).sum()
-                metric = loss
-            elif loss_metric == "MLL":
-                norm, logdet = self._norm_logdet()
-                if masks is None:
-                    t1 = norm.sum()
-                    t2 = d_out / torch.tensor(logdet.shape).prod() * logdet.sum()
-                else:
-                    t1 = norm[(..., *masks, 0)].sum()
-                    t2 = logdet.expand(list(self.shape_batch) + [1])[(..., *masks, 0)].sum()
-                loss = 0.5 * (t1 + t2 + mll_const)
-                metric = -loss
-            else:
-                coeffs = self.coeffs
-                inv_diag = self._inv_diag()
-                t1 = t2 = torch.nan * torch.ones(1)
-                sq = ((coeffs / inv_diag) ** 2 * cv_weights).sum(-1, keepdim=True)
-                loss = sq.sum() if masks is None else sq[(..., *masks, 0)].sum()
-                metric = loss
-            lv = loss.item()
-            if lv < best:
-                best = lv
-                best_params = {k: p.data.clone() for k, p in self.named_parameters()}
-            if (save - lv) > logtol:
-                waited = 0
-                save = best
-            else:
-                waited += 1
-            brk = i == iterations or waited == stop_crit_wait_iterations
-            if h_loss:
-                rec["loss"].append(metric.item())
-            if h_scale:
-                rec["scale"].append(self.scale.detach().cpu())
-            if h_ls:
-                rec["lengthscales"].append(self.lengthscales.detach().cpu())
-            if h_noise:
-                rec["noise"].append(self.noise.detach().cpu())
-            if h_tk:
-                rec["task_kernel"].append(self.gram_matrix_tasks.detach().cpu())
-            if verbose and (i % verbose == 0 or brk):
-                print(" " * verbose_indent + "%16.2e | %-10.2e | %-10.2e | %-10.2e" % (
-                    i, lv, t1.item() if t1.numel() == 1 else torch.nan, t2.item() if t2.numel() == 1 else torch.nan))
-            if brk:
-                break
-            loss.backward()
-            optimizer.step()
-            optimizer.zero_grad()
-        for k, v in best_params.items():
-            setattr(self, k, torch.nn.Parameter(v, requires_grad=getattr(self, k).requires_grad))
-        self._cache = {k: v for k, v in self._cache.items() if not k[2]}
-        self._snap = None
-        data = {"iterations": i}
-        if h_loss:
-            data["loss_hist"] = torch.tensor(rec["loss"])
-        for k, on in (("scale", h_scale), ("lengthscales", h_ls), ("noise", h_noise), ("task_kernel", h_tk)):
-            if on:
-                data[k + "_hist"] = torch.stack(rec[k])
-        return data
+        if not ok:
+            return None
+        return dict(loss_metric=loss_metric, cv_weight=float(cv_weights) if loss_metric == "CV" else 1.0)
+
+    def _loss_generic(self, loss_metric, masks, cv_weights, d_out):
+        """(every iteration recomputes the caches: FASTGP_FORCE_RECOMPILE)"""
+        if loss_metric == "MLL":
+            norm, logdet = self._norm_logdet()
+            return self._mll_of(norm, logdet, masks, d_out, sum(self._ns))
+        if loss_metric == "GCV":
+            return self._gcv_of(*self._gcv_numer_denom(), masks)
+        return self._cv_of(((self.coeffs / self._inv_diag()) ** 2 * cv_weights).sum(-1, keepdim=True), masks)
 
     # ------------------------------------------------------------------ predictions
     def _kmat_rows(self, x, tasks, ns):
@@ -1127,10 +1009,10 @@ _bind_family_classes()
 MT_SPECTRA_CAP = 4 << 30      # bytes of pair spectra the device-resident multitask fits may hold
 
 
-class MtGeneralEngine(object):
+class MtGeneralEngine(FitEngine):
     """Device-resident MLL fit of a general multitask / derivative-informed GP (include/fgp_hip.h ABI 14,
-    fgp_mt_fit_run): the FusedMLL interface _fit_fused drives (run / loss_hist / raw_hist / split_raw), plus
-    the task-kernel parameters (split_task / task_kernel_rows).
+    fgp_mt_fit_run): a fit_engine.FitEngine that also carries the task-kernel parameters (split_task /
+    task_kernel_rows).
 
     raw = [raw_scale, raw_lengthscales (1 or d), raw_noise, raw_factor_task_kernel (T x r), raw_noise_task_kernel
     (T)]; one loss over the data batch (norm summed over B vectors, logdet weighted d_out / numel(logdet) = B,
@@ -1222,22 +1104,10 @@ class MtGeneralEngine(object):
         N.call("fgp_mt_fit_nparams", desc, ctypes.byref(npar))
         assert npar.value == self.n_params
         self.desc = desc
-        self.max_iters = 0
-        self.loss_hist = None
-        self.raw_hist = None
         self.ensure_history(max_iters)
 
-    def ensure_history(self, iters):
-        if iters <= self.max_iters:
-            return
-        new_max = max(iters, 2 * self.max_iters, 16)
-        lh = torch.zeros((new_max, 1, 3), dtype=torch.float64, device=self.device)
-        rh = torch.zeros((new_max, self.n_params), dtype=torch.float64, device=self.device)
-        if self.loss_hist is not None:
-            lh[:self.max_iters] = self.loss_hist
-            rh[:self.max_iters] = self.raw_hist
-        self.loss_hist, self.raw_hist, self.max_iters = lh, rh, new_max
-        self.desc.loss_hist, self.desc.raw_hist = lh.data_ptr(), rh.data_ptr()
+    def _history_moved(self):
+        self.desc.loss_hist, self.desc.raw_hist = self.loss_hist.data_ptr(), self.raw_hist.data_ptr()
 
     def run(self, iter0, iters, final_no_update=False):
         self.ensure_history(iter0 + iters)
@@ -1247,9 +1117,6 @@ class MtGeneralEngine(object):
     def _cut(self, raw_vec, i):
         o = sum(self.sizes[:i])
         return raw_vec[..., o:o + self.sizes[i]]
-
-    def split_raw(self, raw_vec):
-        return self._cut(raw_vec, 0), self._cut(raw_vec, 1), self._cut(raw_vec, 2)
 
     def split_task(self, raw_vec):
         return self._cut(raw_vec, 3), self._cut(raw_vec, 4)

@@ -2,10 +2,9 @@
 
 `WideMLL` is the wide counterpart of fit_engine.FusedMLL for G independent eigen-problems of size n = 2^m: the kernel
 parts ([d, n] shared by every problem, or [G, d, n]), Y[g, k] = sum over the outputs of problem g of |ytilde[k]|^2, the
-raw vector [G scales, G dl lengthscales, G noises], the workspace, the Rprop state and the histories.  It exposes what
-batch._fit_loop, batch._best_raw and FastGP._fit_fused use of a fit engine: G, device, sizes, raw, loss_hist
-[iters, G, 3], raw_hist [iters, n_params], ensure_history, run, split_raw, release_inputs.  Every problem is its own
-GP (own loss, Rprop state and reduction order): a problem's trajectory does not depend on the others in the engine.
+raw vector [G scales, G dl lengthscales, G noises], the workspace, the Rprop state and the histories, behind the
+interface of fit_engine.FitEngine.  Every problem is its own GP (own loss, Rprop state and reduction order): a
+problem's trajectory does not depend on the others in the engine.
 """
 import ctypes
 import math
@@ -13,7 +12,7 @@ import math
 import torch
 
 from . import _native as N
-from .fit_engine import RPROP_ETAS, RPROP_STEPS
+from .fit_engine import RPROP_ETAS, RPROP_STEPS, FitEngine
 from .ops import log2_exact, require_device
 
 
@@ -22,7 +21,7 @@ def wide_mll_constant(d_out, n):
     return 0.5 * d_out * n * math.log(2 * math.pi)
 
 
-class WideMLL(object):
+class WideMLL(FitEngine):
     def __init__(self, family, parts, ysq, raw_scale, raw_lengthscales, raw_noise, logdet_weight, d_out,
                  requires_grad=(True, True, False), lr=0.1, max_iters=1):
         """
@@ -60,8 +59,6 @@ class WideMLL(object):
         self.lr = float(lr)
         self.logdet_weight = float(logdet_weight)
         self.mll_const = wide_mll_constant(d_out, n)
-        self.max_iters = 0
-        self.loss_hist = self.raw_hist = None
         self._desc = N.WideFitDesc(
             family=self.family, log2n=self.m, d=d, G=self.G, parts=self.parts.data_ptr(),
             parts_stride=(d * n if self.parts.dim() == 3 else 0), ysq=self.ysq.data_ptr(), raw=self.raw.data_ptr(),
@@ -76,18 +73,12 @@ class WideMLL(object):
         self._desc.work = self.work.data_ptr()
         self.ensure_history(max(int(max_iters), 16))
 
-    def ensure_history(self, iters):
-        if iters <= self.max_iters:
-            return
-        new_max = max(iters, 2 * self.max_iters, 16)
-        lh = torch.zeros((new_max, self.G, 3), dtype=torch.float64, device=self.device)
-        rh = torch.zeros((new_max, self.n_params), dtype=torch.float64, device=self.device)
-        if self.loss_hist is not None:
-            lh[:self.max_iters] = self.loss_hist
-            rh[:self.max_iters] = self.raw_hist
-        self.loss_hist, self.raw_hist, self.max_iters = lh, rh, new_max
-        self._desc.loss_hist = lh.data_ptr()
-        self._desc.raw_hist = rh.data_ptr()
+    def _hist_problems(self):
+        return self.G
+
+    def _history_moved(self):
+        self._desc.loss_hist = self.loss_hist.data_ptr()
+        self._desc.raw_hist = self.raw_hist.data_ptr()
 
     def run(self, iter0, iters, final_no_update=False):
         """Enqueue `iters` fit iterations writing history rows iter0 .. iter0 + iters - 1 (fgp_wide_fit_run: plain
@@ -95,10 +86,3 @@ class WideMLL(object):
         self.ensure_history(iter0 + iters)
         N.call("fgp_wide_fit_run", self._desc, int(iter0), int(iters), int(bool(final_no_update)),
                N.stream_ptr(self.device))
-
-    def split_raw(self, raw_vec):
-        S, L, Nn = self.sizes
-        return raw_vec[..., :S], raw_vec[..., S:S + L], raw_vec[..., S + L:S + L + Nn]
-
-    def release_inputs(self):
-        """Nothing to drop: the engine owns its buffers for its lifetime (the interface of fit_engine.FusedMLL)."""
