@@ -400,6 +400,51 @@ __device__ __forceinline__ void fwd_reg_passes(T* v, I* col, int tt, const doubl
   if constexpr (S + 4 < P) fwd_reg_passes<P, S + 4, PAD>(v, col, tt, tw);
 }
 
+// The same passes with the table loads of every pass S >= 4 taken out of the transform: FwdTwiddles' constructor
+// requests them all (4 to 12 double2 for 5 <= P <= 12), the caller places it ahead of the work whose latency
+// should cover them (kernel entry, next to its other loads), and the passes between the LDS hand-overs then
+// use registers only.  Same table entries, same butterflies: the same results as fwd_reg_passes, bit for bit.
+template <int P, int S, typename T>
+struct PassTwiddles {
+  static constexpr int RL = PassRL<P, S>::value, GPT = 16 >> RL, TL = (1 << P) / 16;
+  using C = typename Elem<T>::C;
+  C w[GPT][RL];
+  __device__ __forceinline__ PassTwiddles(int tt, const double2* __restrict__ tw) {
+    static_assert(S > 0 && Elem<T>::cx, "pass 0 and real transforms have no table twiddles");
+#pragma unroll
+    for (int j = 0; j < GPT; ++j) {
+      const int blo = (tt + j * TL) & ((1 << S) - 1);
+#pragma unroll
+      for (int q2 = 0; q2 < RL; ++q2) w[j][q2] = twid<C>(tw[blo << (11 - S - q2)]);
+    }
+  }
+};
+template <int P, typename T, int S = 4, bool LIVE = (S < P)>
+struct FwdTwiddles {
+  __device__ __forceinline__ FwdTwiddles(int, const double2* __restrict__) {}
+};
+template <int P, typename T, int S>
+struct FwdTwiddles<P, T, S, true> {
+  PassTwiddles<P, S, T> here;
+  FwdTwiddles<P, T, S + 4> next;
+  __device__ __forceinline__ FwdTwiddles(int tt, const double2* __restrict__ tw) : here(tt, tw), next(tt, tw) {}
+};
+
+template <int P, int S, bool PAD, typename T, typename I>
+__device__ __forceinline__ void fwd_reg_passes_tw(T* v, I* col, int tt, const FwdTwiddles<P, T, S>& w) {
+  constexpr int RL = PassRL<P, S>::value, R = 1 << RL;
+  reg_handover<P, S - 4, 4, S, RL, PAD>(v, col, tt);
+#pragma unroll
+  for (int j = 0; j < 16 / R; ++j) stages_dit<0, RL, S, false>(v + j * R, w.here.w[j]);
+  if constexpr (S + 4 < P) fwd_reg_passes_tw<P, S + 4, PAD>(v, col, tt, w.next);
+}
+template <int P, bool PAD, typename T, typename I>
+__device__ __forceinline__ void fwd_reg_passes(T* v, I* col, int tt, const double2* __restrict__ tw,
+                                               const FwdTwiddles<P, T>& w) {
+  reg_pass<P, 0, PassRL<P, 0>::value, false>(v, tt, tw);     // pass 0: compile-time roots only
+  if constexpr (4 < P) fwd_reg_passes_tw<P, 4, PAD>(v, col, tt, w);
+}
+
 // adjoint (DIF) passes S, S - 4, ..., 0 (start at LastPass<P>::S: the elements the forward passes end on)
 template <int P, int S, bool PAD, typename T, typename I>
 __device__ __forceinline__ void adj_reg_passes(T* v, I* col, int tt, const double2* __restrict__ tw) {

@@ -713,6 +713,27 @@ __global__ __launch_bounds__(kWG, 2) void k_fwd_cols_r2c(Nll a, const double2* _
       y1[j] = yk[nt];
     }
   }
+  // EARLY (the outputs without eigen terms: the spectra build and ytilde): every table entry the kernel uses --
+  // the transform's pass twiddles, each pair job's split twiddle, column 0's two column twiddles and the second
+  // self pair's twiddle -- is requested here, before the tile's loads; the passes and the job loop then touch
+  // registers and LDS only (csrc/fgp_predict.hip k_qf_cols_r2c; DESIGN 3.1 "access rules").  Same entries, same
+  // arithmetic.  The fit's forms keep their loads in place (hoisting them did not pay there).
+  constexpr bool EARLY = OUT == 2 || OUT == 3;
+  constexpr int rh = N1 / 2;     // row of the second self-mirrored element of column 0 (frequencies n/4, 3n/4)
+  double2 wr[EARLY ? JOBS : 1], wcp, wch, wrh;
+  if constexpr (EARLY) {
+    wcp = twmf[col0 ? 0 : cp_gen];
+#pragma unroll
+    for (int j = 0; j < JOBS; ++j) {
+      int sp, rp;
+      int64_t cp;
+      job_primary(j, sp, rp, cp);
+      wr[j] = tw[rp << (24 - m)];
+    }
+    wch = twmf[col0 ? N2 >> 1 : cp_gen];     // column 0's second column, N2/2 (slot HC)
+    wrh = tw[rh << (24 - m)];
+  }
+  const FwdTwiddles<EARLY ? P1 : 4, double2> ftw(tt, tw);     // (P = 4: no table twiddles, nothing loaded)
   double2 v[16];
 #pragma unroll
   for (int j = 0; j < 16 / R0; ++j)
@@ -725,7 +746,8 @@ __global__ __launch_bounds__(kWG, 2) void k_fwd_cols_r2c(Nll a, const double2* _
   double2 mean = column_total<C>(sl, part) * (1.0 / N1);
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] -= mean;
-  fwd_reg_passes<P1, 0, false>(v, col, tt, tw);
+  if constexpr (EARLY) fwd_reg_passes<P1, false>(v, col, tt, tw, ftw);
+  else fwd_reg_passes<P1, 0, false>(v, col, tt, tw);
   if (tt == 0) v[0] += mean * (double)N1;
   // the tile's half-length spectrum into the image
   __syncthreads();
@@ -742,8 +764,8 @@ __global__ __launch_bounds__(kWG, 2) void k_fwd_cols_r2c(Nll a, const double2* _
   double* gb = OUT == 2 ? static_cast<double*>(a.grad_lam) + (int64_t)g * 64 : nullptr;   // basis + (s0 + g) 64
   double2* gh = OUT == 3 ? static_cast<double2*>(a.grad_lam) + (int64_t)g * a.out_stride : nullptr;   // k <= n/2
   const int ns = 1 << a.d;
-  const double2 wcp = twmf[col0 ? 0 : cp_gen];
-#pragma unroll 2
+  if constexpr (!EARLY) wcp = twmf[col0 ? 0 : cp_gen];
+#pragma unroll(EARLY ? JOBS : 2)
   for (int j = 0; j < JOBS; ++j) {
     int sp, rp;
     int64_t cp;
@@ -757,8 +779,15 @@ __global__ __launch_bounds__(kWG, 2) void k_fwd_cols_r2c(Nll a, const double2* _
       ss = HC; rs = N1 - 1 - rp;
     }
     const bool self = col0 && sp == 0 && rp == 0;   // frequencies 0, n/2 and (second pair) n/4, 3n/4
-    const double2 wc = col0 ? twmf[cp] : wcp;
-    const double2 W = cmul(wc, tw[rp << (24 - m)]);                 // w_n^k, k = cp + N2 rp
+    double2 wc, wj;
+    if constexpr (EARLY) {
+      wc = col0 && sp != 0 ? wch : wcp;
+      wj = wr[j];
+    } else {
+      wc = col0 ? twmf[cp] : wcp;
+      wj = tw[rp << (24 - m)];
+    }
+    const double2 W = cmul(wc, wj);                                 // w_n^k, k = cp + N2 rp
     double2* ip = lds + sp * CS + rp;
     double2* is = lds + ss * CS + rs;
     const double2 zk = *ip, zm = *is;
@@ -796,10 +825,11 @@ __global__ __launch_bounds__(kWG, 2) void k_fwd_cols_r2c(Nll a, const double2* _
       if (!self) *is = make_double2(E.x + O.y, O.x - E.y);          // the partner's (conjugate arithmetic)
     }
     if (self) {   // the second self-mirrored element of column 0: row N1/2 (frequencies n/4, 3n/4)
-      constexpr int rh = N1 / 2;
       double2* ih = lds + rh;
       const double2 zh = *ih;
-      const double2 Wh = tw[rh << (24 - m)];
+      double2 Wh;
+      if constexpr (EARLY) Wh = wrh;
+      else Wh = tw[rh << (24 - m)];
       double yc = 0.0, yd = 0.0;
       if constexpr (OUT == 0) {
         yc = yg[(int64_t)rh * N2];

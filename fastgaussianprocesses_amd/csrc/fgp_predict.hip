@@ -540,8 +540,11 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
   const int m = q.log2n;
   const int64_t n = (int64_t)1 << m, nt = n >> 1, N2 = nt >> P1;
   const int64_t tiles = nt >> kTileLog;
-  const int tg = (int)(blockIdx.x / tiles);
-  const int blk = (int)(blockIdx.x % tiles);
+  // tiles in the reverse of the order in which the row launch wrote them: the intermediate of a benchmark-sized
+  // launch is twice the Infinity Cache, and the rows written last are the ones still on the die
+  const unsigned bid = gridDim.x - 1 - blockIdx.x;
+  const int tg = (int)(bid / tiles);
+  const int blk = (int)(bid % tiles);
   const int tid = threadIdx.x;
   const int sl = tid % C, tt = tid / C;
   const double2* wk = static_cast<const double2*>(q.work) + (int64_t)tg * n + (int64_t)blk * kTile + sl;
@@ -560,7 +563,11 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
       sp = HC; rp = rr - N1 / 2; cp = N2 >> 1;
     }
   };
+  // every pair job's weights and split twiddle, column 0's two column twiddles and the second self pair's
+  // weights and twiddle are requested here, before the column transform: the job loop below touches only
+  // registers and LDS (the one-loop form waited for each job's table loads in turn, DESIGN 3.1 "access rules")
   double w0[JOBS], w1[JOBS];
+  double2 wr[JOBS];
 #pragma unroll
   for (int j = 0; j < JOBS; ++j) {
     int sp, rp;
@@ -569,7 +576,14 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
     const double* wp = wa + cp + (int64_t)rp * N2;
     w0[j] = wp[0];
     w1[j] = wp[nt];
+    wr[j] = tw[rp << (24 - m)];
   }
+  const double2 wcp = twmf[col0 ? 0 : cp_gen];              // column twiddle of slot sp = jq (column 0: of column 0)
+  const double2 wch = twmf[col0 ? N2 >> 1 : cp_gen];        // column 0's second column, N2/2 (slot HC)
+  constexpr int rh = N1 / 2;     // second self-mirrored element of column 0 (frequencies n/4, 3n/4)
+  const double2 wrh = tw[rh << (24 - m)];
+  const double wh0 = wa[(int64_t)rh * N2], wh1 = wa[(int64_t)rh * N2 + nt];
+  const FwdTwiddles<P1, double2> ftw(tt, tw);     // and the transform's own pass twiddles
   double2 v[16];
 #pragma unroll
   for (int j = 0; j < 16 / R0; ++j)
@@ -582,7 +596,7 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
   const double2 mean = column_total<C>(sl, part) * (1.0 / N1);
 #pragma unroll
   for (int k = 0; k < 16; ++k) v[k] -= mean;
-  fwd_reg_passes<P1, 0, false>(v, col, tt, tw);
+  fwd_reg_passes<P1, false>(v, col, tt, tw, ftw);
   if (tt == 0) v[0] += mean * (double)N1;
   __syncthreads();
 #pragma unroll
@@ -591,7 +605,6 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
     for (int t = 0; t < RLAST; ++t) col[pass_pos<P1, SL, RLL>(tt, j, t)] = v[j * RLAST + t];
   __syncthreads();
   double acc2 = 0.0, acc1 = 0.0;
-  const double2 wcp = twmf[col0 ? 0 : cp_gen];
   auto split = [&](double2 zk, double2 zm, double2 W, double wk0, double wk1) {
     const double2 S = make_double2(zk.x + zm.x, zk.y - zm.y);
     const double2 Dd = make_double2(zk.x - zm.x, zk.y + zm.y);
@@ -600,7 +613,7 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
     const double2 A1 = make_double2(0.5 * (S.x - wd.y), 0.5 * (S.y + wd.x));
     return __builtin_fma(wk0, sqabs(A0), wk1 * sqabs(A1));
   };
-#pragma unroll 2
+#pragma unroll
   for (int j = 0; j < JOBS; ++j) {
     int sp, rp;
     int64_t cp;
@@ -614,14 +627,13 @@ __global__ __launch_bounds__(kWG, 2) void k_qf_cols_r2c(QfArgs q, const double2*
       ss = HC; rs = N1 - 1 - rp;
     }
     const bool self = col0 && sp == 0 && rp == 0;
-    const double2 wc = col0 ? twmf[cp] : wcp;
-    const double2 W = cmul(wc, tw[rp << (24 - m)]);
+    const double2 wc = col0 && sp != 0 ? wch : wcp;
+    const double2 W = cmul(wc, wr[j]);
     const double s = split(lds[sp * CS + rp], lds[ss * CS + rs], W, w0[j], w1[j]);
     if (self) {
       acc1 += s;
-      constexpr int rh = N1 / 2;     // second self-mirrored element of column 0 (frequencies n/4, 3n/4)
       const double2 zh = lds[rh];
-      acc1 += split(zh, zh, tw[rh << (24 - m)], wa[(int64_t)rh * N2], wa[(int64_t)rh * N2 + nt]);
+      acc1 += split(zh, zh, wrh, wh0, wh1);
     } else {
       acc2 += s;
     }
