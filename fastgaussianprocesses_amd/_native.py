@@ -116,6 +116,7 @@ class WideFitDesc(ctypes.Structure):
         ("rprop_prev", _c_vp), ("rprop_step", _c_vp), ("lr", _c_dbl),
         ("eta_minus", _c_dbl), ("eta_plus", _c_dbl), ("step_min", _c_dbl), ("step_max", _c_dbl),
         ("loss_hist", _c_vp), ("raw_hist", _c_vp), ("grad_out", _c_vp), ("work", _c_vp),
+        ("loss_metric", _c_int), ("cv_weight", _c_dbl),
     ]
 
 

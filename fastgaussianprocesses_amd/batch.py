@@ -23,6 +23,7 @@ import torch
 from . import _native as N
 from . import ops
 from .wide_fit import WideMLL
+from .fast_gp import _scalar_weight
 from .fit_engine import FusedMLL, LatticePartsGen, cached_engine, fused_lam, mll_constant, spec_basis, spec_basis_gen, spec_inv_eig, spectral_wanted
 from .fit_loop import StopRule, chunk_schedule, first_minimum
 
@@ -127,6 +128,20 @@ def _best_raw(eng, best, dl):
     return eng.raw_hist[idx_r, idx_c].reshape(P, 2 + dl)
 
 
+def _loss_args(gps, loss_metric, cv_weights):
+    """(loss_metric, cv_weight) of a batch fit: GCV / CV only for wide GPs (wide_fit.WideMLL), with ONE CV weight."""
+    assert isinstance(loss_metric, str) and loss_metric.upper() in ["MLL", "GCV", "CV"]
+    loss_metric = loss_metric.upper()
+    if loss_metric == "MLL":
+        return loss_metric, 1.0
+    assert gps[0].d > N.MAX_D, \
+        "a narrow batch (d <= %d) fits the MLL only: loss_metric=%r needs each GP's own fit()" % (N.MAX_D, loss_metric)
+    if loss_metric == "CV":
+        assert _scalar_weight(cv_weights), "a batch CV fit takes a scalar cv_weights"
+        return loss_metric, float(cv_weights)
+    return loss_metric, 1.0
+
+
 def _check_batch(gps):
     assert len(gps) > 0
     g0 = gps[0]
@@ -192,7 +207,7 @@ def _basis_for(gps, n, parts, gen):
     return spec_basis(g0._FAMILY, p, n)
 
 
-def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False):
+def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False, loss_metric="MLL", cv_weight=1.0):
     g0 = gps[0]
     dl = g0.raw_lengthscales.shape[-1]
     d_out = int(math.prod(g0.shape_batch))
@@ -202,7 +217,8 @@ def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False):
     kw = dict(logdet_weight=float(d_out), requires_grad=g0._raw_requires_grad(), lr=1e-1 if lr is None else lr,
               max_iters=iterations + 1)
     if g0.d > N.MAX_D:
-        return WideMLL(g0._FAMILY, parts, ysq, *raw, d_out=d_out, **kw)
+        return WideMLL(g0._FAMILY, parts, ysq, *raw, d_out=d_out, loss_metric=loss_metric, cv_weight=cv_weight, **kw)
+    assert loss_metric == "MLL"
     kw.update(mll_const=mll_constant(d_out, n), basis=basis, per_problem=True)
     if cached and basis is not None:
         # the batch's spectral engine, reused across fits of this geometry (fit_engine.cached_engine)
@@ -210,36 +226,42 @@ def _engine(gps, n, ysq, parts, gen, lr, iterations, basis=None, cached=False):
     return FusedMLL(g0._FAMILY, parts, ysq, *raw, parts_per_problem=True, gen=None if basis is not None else gen, **kw)
 
 
-def _fit_data(eng, stops, losses, store):
-    """The per-GP data dicts of _fit_loop's result (losses None: the histories are still on the device)."""
+def _fit_data(eng, stops, losses, store, loss_metric="MLL"):
+    """The per-GP data dicts of _fit_loop's result (losses None: the histories are still on the device); the loss
+    history holds -loss for the MLL and the loss itself for GCV / CV (abstract_gp.py:242-273)."""
     out = [{"iterations": s} for s in stops]
     if store:
+        sgn = -1.0 if loss_metric == "MLL" else 1.0
         lh = eng.loss_hist[:stops[0] + 1, :, 0].cpu() if losses is None else None
         for p, data in enumerate(out):
-            data["loss_hist"] = -lh[:, p].clone() if losses is None else torch.tensor([-v for v in losses[p]])
+            data["loss_hist"] = sgn * lh[:, p].clone() if losses is None else torch.tensor([sgn * v for v in losses[p]])
     return out
 
 
 def fit_batched(gps, iterations=5000, lr=None, stop_crit_improvement_threshold=5e-2, stop_crit_wait_iterations=10,
-                store_hists=False, store_loss_hist=False):
-    """Fit independent single-problem GPs (same class, n, d, alpha, shapes) with the fused MLL loop.
+                store_hists=False, store_loss_hist=False, loss_metric="MLL", cv_weights=1):
+    """Fit independent single-problem GPs (same class, n, d, alpha, shapes) with the fused MLL loop; wide GPs
+    (9 <= d <= 64) also by loss_metric "GCV" / "CV" (a scalar cv_weights), one loss and Rprop state per GP.
 
     Returns the list of per-GP `data` dicts that `gp.fit(iterations=..., verbose=0, ...)` would return."""
     g0, n = _check_batch(gps)
-    eng = batched_engine(gps, iterations, lr)
+    loss_metric, cv_weight = _loss_args(gps, loss_metric, cv_weights)
+    eng = (batched_engine(gps, iterations, lr) if loss_metric == "MLL" else
+           batched_engine(gps, iterations, lr, loss_metric=loss_metric, cv_weight=cv_weight))
     stops, best, losses = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
     _set_raw(gps, _best_raw(eng, best, g0.raw_lengthscales.shape[-1]).clone(), g0.raw_lengthscales.shape[-1])
-    return _fit_data(eng, stops, losses, store_hists or store_loss_hist)
+    return _fit_data(eng, stops, losses, store_hists or store_loss_hist, loss_metric)
 
 
-def batched_engine(gps, iterations, lr=None):
+def batched_engine(gps, iterations, lr=None, loss_metric="MLL", cv_weight=1.0):
     """The FusedMLL (per_problem mode) over the GPs' stacked problems: Y = |ytilde|^2 rows and raw
     parameters stacked, the kernel parts regenerated in the kernels for lattice GPs sharing one
     generating vector (otherwise a stacked [P, d, n] parts array)."""
     n = gps[0]._nh
     parts, gen = _parts_source(gps, n)
     ysq = torch.stack([gp._ysq(*gp._problem_batch())[0] for gp in gps])
-    return _engine(gps, n, ysq, parts, gen, lr, iterations, basis=_basis_for(gps, n, parts, gen))
+    return _engine(gps, n, ysq, parts, gen, lr, iterations, basis=_basis_for(gps, n, parts, gen),
+                   loss_metric=loss_metric, cv_weight=cv_weight)
 
 
 class GPBatch(object):
@@ -367,16 +389,18 @@ class GPBatch(object):
 
     # ---------------------------------------------------------------------------- fit
     def fit(self, iterations=5000, lr=None, stop_crit_improvement_threshold=5e-2, stop_crit_wait_iterations=10,
-            store_hists=False, store_loss_hist=False):
-        """Every GP's AbstractGP.fit(loss_metric="MLL", verbose=0) in one device loop; returns the list of
-        per-GP data dicts."""
+            store_hists=False, store_loss_hist=False, loss_metric="MLL", cv_weights=1):
+        """Every GP's AbstractGP.fit(loss_metric=..., verbose=0) in one device loop (GCV / CV: wide GPs only, a scalar
+        cv_weights); returns the list of per-GP data dicts."""
+        loss_metric, cv_weight = _loss_args(self.gps, loss_metric, cv_weights)
         parts, gen = self._source()
-        eng = _engine(self.gps, self.n, self.ysq(), parts, gen, lr, iterations, basis=self.basis(), cached=True)
+        eng = _engine(self.gps, self.n, self.ysq(), parts, gen, lr, iterations, basis=self.basis(), cached=True,
+                      loss_metric=loss_metric, cv_weight=cv_weight)
         stops, best_i, losses = _fit_loop(eng, iterations, stop_crit_improvement_threshold, stop_crit_wait_iterations)
         best = _best_raw(eng, best_i, self.dl)
         self.set_raw(best)
         self._st["raw"] = best
-        out = _fit_data(eng, stops, losses, store_hists or store_loss_hist)
+        out = _fit_data(eng, stops, losses, store_hists or store_loss_hist, loss_metric)
         eng.release_inputs()
         return out
 

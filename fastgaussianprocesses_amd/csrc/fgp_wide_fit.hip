@@ -10,6 +10,11 @@
 //   step      k_wide_fit_step (new)             two-level sums, loss, histories, chain rule to the raw parameters,
 //                                               Rprop (rprop_update, fgp_nll.h), the natural rows of the next k1
 //
+// fgp_wide_fit_desc.loss_metric GCV / CV (AbstractGP.fit's alternative losses, abstract_gp.py:242-273; the closed forms
+// above loss_terms in fgp_spectral.hip): g~ needs the global sums N1 and T, so `terms` becomes two passes over lambda
+// and Y -- k_wide_fit_loss_sums (the partials, lambda left in place) and k_wide_fit_loss_grad (g~ over lambda) -- ten
+// launches per iteration instead of nine; the MLL sequence is untouched.
+//
 // No host synchronisation, no device-to-host copy, no atomics, no inter-workgroup hand-off: every kernel reads what
 // the launch before it wrote.  The lattice lambda of a real even k1 is real up to rounding; its real part is taken
 // (Re(1/ev) and log|ev| differ from the complex forms by O((Im/Re)^2), below one rounding), so g~ is real and its
@@ -117,6 +122,179 @@ __global__ __launch_bounds__(kWG) void k_wide_fit_eig(double* __restrict__ lam, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// GCV / CV.  With ev_k = sqrt(n) Re(lambda_k) + noise, lambda'_k = sqrt(n) Re(lambda_k), r = 1 / ev_k:
+//   N1 = sum Y_k r^2,  S1 = sum Y_k r^3,  GCV: T = sum r, S2 = sum r^2;  CV: T = sum 1 / lambda'_k
+//   GCV: D = (T / n)^2, loss = N1 / D, c1 = -2 / D, c2 = 2 N1 T / (n^2 D^2), w2_k = r^2
+//   CV:  I = T / n, loss = w N1 / I^2, c1 = -2 w / I^2, c2 = 2 w N1 / (n I^3), w2_k = 1 / lambda'_k^2
+//   g~_k = dL/dlambda_k = sqrt(n) (c1 Y_k r^3 + c2 w2_k),  dL/dnoise = c1 S1 (+ c2 S2, GCV)
+// Partials [G][4][nbe] = (N1, T, S1, S2); the CV loop leaves row 3 unwritten and unread.
+constexpr int kWfLossQ = 4;
+
+// A lane's kWfV groups of (Y_k, Y_k+1, Re lambda_k, Re lambda_k+1), zero past the row: k_wide_fit_eig's load pattern,
+// every 16-byte load issued before the arithmetic.
+template <int FAM>
+__device__ __forceinline__ void wide_fit_load(const double* __restrict__ yrow, const double* __restrict__ lrow,
+                                              int64_t base, int64_t n, double (&y0)[kWfV], double (&y1)[kWfV],
+                                              double (&l0)[kWfV], double (&l1)[kWfV]) {
+#pragma unroll
+  for (int v = 0; v < kWfV; ++v) {
+    const int64_t k = base + (int64_t)v * 2 * kWG;
+    y0[v] = y1[v] = 0.0;
+    l0[v] = l1[v] = 0.0;
+    if (k + 1 < n) {
+      const double2 yy = *reinterpret_cast<const double2*>(yrow + k);
+      y0[v] = yy.x;
+      y1[v] = yy.y;
+      if constexpr (FAM == 0) {
+        const double2 a = *reinterpret_cast<const double2*>(lrow + 2 * k);
+        const double2 b = *reinterpret_cast<const double2*>(lrow + 2 * k + 2);
+        l0[v] = a.x;
+        l1[v] = b.x;
+      } else {
+        const double2 a = *reinterpret_cast<const double2*>(lrow + k);
+        l0[v] = a.x;
+        l1[v] = a.y;
+      }
+    } else if (k < n) {
+      y0[v] = yrow[k];
+      l0[v] = lrow[FAM == 0 ? 2 * k : k];
+    }
+  }
+}
+
+// Level 2 of a two-level sum: a lane over every kWG-th partial in ascending order, then block_sum's fixed tree (the
+// order k_wide_fit_step's MLL sums use).  Every thread gets the total.
+__device__ __forceinline__ double wide_fit_total(const double* __restrict__ pq, int nbe, double* red) {
+  double a = 0.0;
+  for (int c = threadIdx.x; c < nbe; c += kWG) a += pq[c];
+  return block_sum(a, red);
+}
+
+// loss, c1, c2 and the history terms of one problem from its totals: ONE sequence of operations for
+// k_wide_fit_loss_grad and k_wide_fit_step, whose coefficients are therefore the same bits.
+struct WideLossCoef {
+  double loss, c1, c2, t1, t2;
+};
+
+template <bool CV>
+__device__ __forceinline__ WideLossCoef wide_loss_coef(double N1, double T, double n, double w) {
+  WideLossCoef c;
+  if constexpr (CV) {
+    const double I = T / n, I2 = I * I;
+    c.loss = w * N1 / I2;
+    c.c1 = -2.0 * w / I2;
+    c.c2 = 2.0 * w * N1 / (n * I2 * I);
+    c.t1 = c.t2 = NAN;
+  } else {
+    const double q = T / n, D = q * q;
+    c.loss = N1 / D;
+    c.c1 = -2.0 / D;
+    c.c2 = 2.0 * N1 * T / (n * n * D * D);
+    c.t1 = N1;
+    c.t2 = D;
+  }
+  return c;
+}
+
+// Pass 1 over frequencies [blockIdx.x kWfBlock, +kWfBlock) of problem g = blockIdx.y: the partials; lambda stays.
+template <int FAM, bool CV>
+__global__ __launch_bounds__(kWG) void k_wide_fit_loss_sums(const double* __restrict__ lam,
+                                                            const double* __restrict__ ysq,
+                                                            const double* __restrict__ raw_noise, int64_t n,
+                                                            double sqrtn, int nbe, double* __restrict__ partial) {
+  __shared__ double red[kWG / 64];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.y;
+  const double noise = exp(raw_noise[g]);
+  const double* yrow = ysq + (int64_t)g * n;
+  const double* lrow = lam + (int64_t)g * n * (FAM == 0 ? 2 : 1);
+  const int64_t base = (int64_t)blockIdx.x * kWfBlock + 2 * tid;
+  double y0[kWfV], y1[kWfV], l0[kWfV], l1[kWfV];
+  wide_fit_load<FAM>(yrow, lrow, base, n, y0, y1, l0, l1);
+  double s_n1 = 0.0, s_t = 0.0, s_1 = 0.0, s_2 = 0.0;
+#pragma unroll
+  for (int v = 0; v < kWfV; ++v) {
+    const int64_t k = base + (int64_t)v * 2 * kWG;
+    if (k >= n) continue;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      if (e == 1 && k + 1 >= n) continue;
+      const double lp = sqrtn * (e ? l1[v] : l0[v]), Y = e ? y1[v] : y0[v];
+      const double r = 1.0 / (lp + noise);
+      const double r2 = r * r, yr2 = Y * r2;
+      s_n1 += yr2;
+      s_1 += yr2 * r;
+      if constexpr (CV) {
+        s_t += 1.0 / lp;
+      } else {
+        s_t += r;
+        s_2 += r2;
+      }
+    }
+  }
+  s_n1 = block_sum(s_n1, red);
+  s_t = block_sum(s_t, red);
+  s_1 = block_sum(s_1, red);
+  if constexpr (!CV) s_2 = block_sum(s_2, red);
+  if (tid == 0) {
+    double* pg = partial + (int64_t)g * kWfLossQ * nbe + blockIdx.x;
+    pg[0] = s_n1;
+    pg[(int64_t)nbe] = s_t;
+    pg[2 * (int64_t)nbe] = s_1;
+    if constexpr (!CV) pg[3 * (int64_t)nbe] = s_2;
+  }
+}
+
+// Pass 2, same geometry: every workgroup re-sums its problem's N1 and T partials in k_wide_fit_step's order (no
+// coefficient launch between the passes, no hand-off), forms c1 and c2 and writes g~ over lambda (lattice: (g~, 0)).
+template <int FAM, bool CV>
+__global__ __launch_bounds__(kWG) void k_wide_fit_loss_grad(double* __restrict__ lam, const double* __restrict__ ysq,
+                                                            const double* __restrict__ raw_noise, int64_t n,
+                                                            double sqrtn, double w, int nbe,
+                                                            const double* __restrict__ partial) {
+  __shared__ double red[kWG / 64];
+  const int tid = threadIdx.x;
+  const int g = blockIdx.y;
+  const double noise = exp(raw_noise[g]);
+  const double* yrow = ysq + (int64_t)g * n;
+  double* lrow = lam + (int64_t)g * n * (FAM == 0 ? 2 : 1);
+  const int64_t base = (int64_t)blockIdx.x * kWfBlock + 2 * tid;
+  double y0[kWfV], y1[kWfV], l0[kWfV], l1[kWfV];
+  wide_fit_load<FAM>(yrow, lrow, base, n, y0, y1, l0, l1);
+  const double* pg = partial + (int64_t)g * kWfLossQ * nbe;
+  const double N1 = wide_fit_total(pg, nbe, red);
+  const double T = wide_fit_total(pg + nbe, nbe, red);
+  const WideLossCoef c = wide_loss_coef<CV>(N1, T, (double)n, w);
+#pragma unroll
+  for (int v = 0; v < kWfV; ++v) {
+    const int64_t k = base + (int64_t)v * 2 * kWG;
+    if (k >= n) continue;
+    const bool pair = k + 1 < n;
+    double gt[2] = {0.0, 0.0};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      if (e == 1 && !pair) continue;
+      const double lp = sqrtn * (e ? l1[v] : l0[v]), Y = e ? y1[v] : y0[v];
+      const double r = 1.0 / (lp + noise);
+      const double r2 = r * r;
+      double w2 = r2;
+      if constexpr (CV) {
+        const double rl = 1.0 / lp;
+        w2 = rl * rl;
+      }
+      gt[e] = sqrtn * (c.c1 * (Y * r2 * r) + c.c2 * w2);
+    }
+    if constexpr (FAM == 0) {
+      *reinterpret_cast<double2*>(lrow + 2 * k) = make_double2(gt[0], 0.0);
+      if (pair) *reinterpret_cast<double2*>(lrow + 2 * k + 2) = make_double2(gt[1], 0.0);
+    } else {
+      if (pair) *reinterpret_cast<double2*>(lrow + k) = make_double2(gt[0], gt[1]);
+      else lrow[k] = gt[0];
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The step of problem g = blockIdx.x (one workgroup per problem).  raw = [G scales, G dl lengthscales, G noises].
 //   mode 0  only the natural rows of the current raw parameters (before the first k1 of a run; init: a new fit's
 //           Rprop state prev = 0, step = lr)
@@ -124,18 +302,25 @@ __global__ __launch_bounds__(kWG) void k_wide_fit_eig(double* __restrict__ lam, 
 //   mode 2  the same, the Rprop step of the parameters that require a gradient, and the natural rows of the new ones
 // Sums: level 1 = the per-workgroup partials of k_wide_fit_eig / k_wide_k1_bwd, level 2 here, a lane over every
 // kWG-th partial in ascending order, then block_sum's fixed tree.
+// LOSS = FGP_LOSS_GCV / FGP_LOSS_CV: pe is k_wide_fit_loss_sums' [G][4][nbe]; the history row is (loss, N1, D) /
+// (loss, NaN, NaN) as k_spec_loss_step writes it, dL/dnoise = c1 S1 (+ c2 S2, GCV); mll_const and w are not used.
 struct WideFitStep {
   Fit f;
   int G, d, dl, nbe;
   double w, lr;
-  const double* pe;          // [G][3][nbe]
+  const double* pe;          // [G][3][nbe]; GCV / CV: [G][4][nbe]
   const double* dscale;      // [G]      dL/dscale
   const double* dls;         // [G][d]   dL/dl_j
   double* nat_scale;         // [G]
   double* nat_ls;            // [G][d]
 };
 
-__global__ __launch_bounds__(kWG) void k_wide_fit_step(WideFitStep s, int iter, int mode, int init) {
+struct WideFitLoss {
+  double n, cv_weight;
+};
+
+template <int LOSS>
+__global__ __launch_bounds__(kWG) void k_wide_fit_step(WideFitStep s, int iter, int mode, int init, WideFitLoss x) {
   __shared__ double red[kWG / 64];
   const int tid = threadIdx.x;
   const int g = blockIdx.x;
@@ -143,13 +328,23 @@ __global__ __launch_bounds__(kWG) void k_wide_fit_step(WideFitStep s, int iter, 
   const Fit& f = s.f;
   const int p_scale = g, p_ls = G + g * dl, p_noise = G + G * dl + g;
   if (mode != 0) {
-    double sums[3];
+    constexpr bool CV = LOSS == FGP_LOSS_CV;
+    constexpr int NQ = LOSS == FGP_LOSS_MLL ? 3 : kWfLossQ;
+    double sums[NQ];
+    WideLossCoef lc{};
+    if constexpr (LOSS == FGP_LOSS_MLL) {
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const double* pq = s.pe + ((int64_t)g * 3 + q) * s.nbe;
-      double a = 0.0;
-      for (int c = tid; c < s.nbe; c += kWG) a += pq[c];
-      sums[q] = block_sum(a, red);
+      for (int q = 0; q < 3; ++q) {
+        const double* pq = s.pe + ((int64_t)g * 3 + q) * s.nbe;
+        double a = 0.0;
+        for (int c = tid; c < s.nbe; c += kWG) a += pq[c];
+        sums[q] = block_sum(a, red);
+      }
+    } else {
+      sums[3] = 0.0;
+#pragma unroll
+      for (int q = 0; q < (CV ? 3 : 4); ++q) sums[q] = wide_fit_total(s.pe + ((int64_t)g * NQ + q) * s.nbe, s.nbe, red);
+      lc = wide_loss_coef<CV>(sums[0], sums[1], x.n, x.cv_weight);
     }
     if (tid < 2 + dl) {
       int p, rg;
@@ -174,7 +369,9 @@ __global__ __launch_bounds__(kWG) void k_wide_fit_step(WideFitStep s, int iter, 
         p = p_noise;
         rg = f.noise_rg;
         nat = exp(f.raw[p]);
-        gnat = 0.5 * sums[2];
+        if constexpr (LOSS == FGP_LOSS_MLL) gnat = 0.5 * sums[2];
+        else if constexpr (CV) gnat = lc.c1 * sums[2];
+        else gnat = lc.c1 * sums[2] + lc.c2 * sums[3];
       }
       const double graw = nat * gnat;          // exp transforms: d nat / d raw = nat
       f.raw_hist[(int64_t)iter * f.n_params + p] = f.raw[p];
@@ -182,11 +379,17 @@ __global__ __launch_bounds__(kWG) void k_wide_fit_step(WideFitStep s, int iter, 
       if (mode == 2 && rg) rprop_update(f, p, graw);
     }
     if (tid == 0) {
-      const double t2 = s.w * sums[1];
       double* lh = f.loss_hist + ((int64_t)iter * G + g) * 3;
-      lh[0] = 0.5 * (sums[0] + t2) + f.mll_const;
-      lh[1] = sums[0];
-      lh[2] = t2;
+      if constexpr (LOSS == FGP_LOSS_MLL) {
+        const double t2 = s.w * sums[1];
+        lh[0] = 0.5 * (sums[0] + t2) + f.mll_const;
+        lh[1] = sums[0];
+        lh[2] = t2;
+      } else {
+        lh[0] = lc.loss;
+        lh[1] = lc.t1;
+        lh[2] = lc.t2;
+      }
     }
     if (mode != 2) return;
     __syncthreads();
@@ -204,7 +407,7 @@ struct WideFitPlan {
   int64_t n;
   int nbe;                                       // k_wide_fit_eig workgroups per problem
   bool lat, r2c;
-  int64_t o_scale, o_ls, o_dscale, o_dls, o_a, o_b, o_w, o_pe, o_pb, len;   // offsets into work, in doubles
+  int64_t o_scale, o_ls, o_dscale, o_dls, o_a, o_b, o_w, o_pe, o_pb, o_pl, len;   // offsets into work, in doubles
 };
 
 static int64_t even(int64_t v) { return (v + 1) & ~(int64_t)1; }
@@ -222,6 +425,10 @@ static int wide_fit_plan(const char* fn, const fgp_wide_fit_desc* a, WideFitPlan
   if (a->parts_stride != 0 && a->parts_stride != (int64_t)a->d * p.n)
     return set_error(kErrInvalid, "%s: parts_stride=%lld is neither 0 nor d n", fn, (long long)a->parts_stride);
   if ((int64_t)a->G * (2 + a->dl) > (int64_t)1 << 30) return set_error(kErrInvalid, "%s: G=%d too large", fn, a->G);
+  if (a->loss_metric != FGP_LOSS_MLL && a->loss_metric != FGP_LOSS_GCV && a->loss_metric != FGP_LOSS_CV)
+    return set_error(kErrInvalid, "%s: loss_metric=%d not FGP_LOSS_MLL / _GCV / _CV", fn, a->loss_metric);
+  if (a->loss_metric == FGP_LOSS_CV && !std::isfinite(a->cv_weight))
+    return set_error(kErrInvalid, "%s: cv_weight is not finite", fn);
   p.lat = a->family == FGP_FAMILY_LATTICE;
   p.r2c = use_r2c(read_switches(), p.lat, a->log2n);
   p.nbe = (int)((p.n + kWfBlock - 1) / kWfBlock);
@@ -236,8 +443,29 @@ static int wide_fit_plan(const char* fn, const fgp_wide_fit_desc* a, WideFitPlan
   p.o_w = o, o += p.lat ? 2 * G * n : 0;                // the lattice transforms' scratch
   p.o_pe = o, o += even(G * 3 * p.nbe);
   p.o_pb = o, o += even(G * (1 + d) * ((n + kWG - 1) / kWG));
+  // GCV / CV: k_wide_fit_loss_sums' partials, after everything the MLL lays out (whose length stays as it was)
+  p.o_pl = o, o += a->loss_metric == FGP_LOSS_MLL ? 0 : even(G * kWfLossQ * p.nbe);
   p.len = o;
   return kOk;
+}
+
+// The two GCV / CV passes of one iteration over lambda (B) and Y.
+template <int FAM, bool CV>
+static int wide_fit_loss_terms_t(dim3 grid, double* B, const double* ysq, const double* raw_noise, int64_t n,
+                                 double sqrtn, double w, int nbe, double* pe, hipStream_t st) {
+  k_wide_fit_loss_sums<FAM, CV><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
+  const int rc = check_launch("k_wide_fit_loss_sums");
+  if (rc != kOk) return rc;
+  k_wide_fit_loss_grad<FAM, CV><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+  return check_launch("k_wide_fit_loss_grad");
+}
+
+static int wide_fit_loss_terms(bool lat, bool cv, dim3 grid, double* B, const double* ysq, const double* raw_noise,
+                               int64_t n, double sqrtn, double w, int nbe, double* pe, hipStream_t st) {
+  if (lat) return cv ? wide_fit_loss_terms_t<0, true>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st)
+                     : wide_fit_loss_terms_t<0, false>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st);
+  return cv ? wide_fit_loss_terms_t<1, true>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st)
+            : wide_fit_loss_terms_t<1, false>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st);
 }
 
 static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int iter0, int iters, int final_no_update,
@@ -260,11 +488,19 @@ static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int it
   s.f.eta_minus = a->eta_minus, s.f.eta_plus = a->eta_plus, s.f.step_min = a->step_min, s.f.step_max = a->step_max;
   s.G = G, s.d = d, s.dl = a->dl, s.nbe = p.nbe;
   s.w = a->logdet_weight, s.lr = a->lr;
+  if (a->loss_metric != FGP_LOSS_MLL) pe = work + p.o_pl;
   s.pe = pe, s.dscale = dscale, s.dls = dls, s.nat_scale = nat_scale, s.nat_ls = nat_ls;
   const double* raw_noise = a->raw + (int64_t)G * (1 + a->dl);
   const double sqrtn = std::sqrt((double)n);
-  k_wide_fit_step<<<G, kWG, 0, st>>>(s, 0, 0, iter0 == 0 && a->lr > 0.0);
-  int rc = check_launch("k_wide_fit_step");
+  const int loss = a->loss_metric;
+  const WideFitLoss x{(double)n, a->cv_weight};
+  auto step = [&](int iter, int mode, int init) {
+    if (loss == FGP_LOSS_MLL) k_wide_fit_step<FGP_LOSS_MLL><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
+    else if (loss == FGP_LOSS_GCV) k_wide_fit_step<FGP_LOSS_GCV><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
+    else k_wide_fit_step<FGP_LOSS_CV><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
+    return check_launch("k_wide_fit_step");
+  };
+  int rc = step(0, 0, iter0 == 0 && a->lr > 0.0);
   for (int it = 0; it < iters && rc == kOk; ++it) {
     // k1 (per problem when every problem has its own parts: fgp_wide_k1 takes ONE parts array)
     if (a->parts_stride == 0) {
@@ -280,9 +516,14 @@ static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int it
     else rc = fgp_fftbr(A, n, 1, B, G, m, 1, st);
     if (rc != kOk) break;
     const dim3 grid((unsigned)p.nbe, (unsigned)G);
-    if (p.lat) k_wide_fit_eig<0><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
-    else k_wide_fit_eig<1><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
-    rc = check_launch("k_wide_fit_eig");
+    if (loss == FGP_LOSS_MLL) {
+      if (p.lat) k_wide_fit_eig<0><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
+      else k_wide_fit_eig<1><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
+      rc = check_launch("k_wide_fit_eig");
+    } else {
+      rc = wide_fit_loss_terms(p.lat, loss == FGP_LOSS_CV, grid, B, a->ysq, raw_noise, n, sqrtn, a->cv_weight, p.nbe, pe,
+                               st);
+    }
     if (rc != kOk) break;
     // u = dL/dk1: the adjoint transform of g~ (lattice: the real part)
     if (!p.lat) rc = fgp_fwht(B, n, A, G, m, 1, st);
@@ -298,8 +539,7 @@ static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int it
     }
     if (rc != kOk) break;
     const bool last = it + 1 == iters;
-    k_wide_fit_step<<<G, kWG, 0, st>>>(s, iter0 + it, (last && final_no_update) ? 1 : 2, 0);
-    rc = check_launch("k_wide_fit_step");
+    rc = step(iter0 + it, (last && final_no_update) ? 1 : 2, 0);
   }
   return rc;
 }

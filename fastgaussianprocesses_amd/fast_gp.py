@@ -52,6 +52,13 @@ SPEC_POST_VAR_MAX_N = 4096            # test points per fgp_spec_post_var call (
 SPEC_POST_VAR_WORK = 1 << 30          # bytes of row products + row spectra per slice of test points
 
 
+def _scalar_weight(cv_weights):
+    """cv_weights is ONE weight for every point (the device CV loss: the Parseval form needs a scalar)."""
+    if torch.is_tensor(cv_weights):
+        return cv_weights.numel() == 1
+    return bool(np.isscalar(cv_weights))
+
+
 def _as_size(s):
     if s is None or isinstance(s, torch.Size):
         return s
@@ -758,12 +765,14 @@ class AbstractFastGP(torch.nn.Module):
         """The keyword arguments of _fit_fused (ysq, d_out, loss_metric, cv_weight) when this fit runs on the device,
         else None: the default optimizer; the MLL inside _fused_ok -- with masks, when one eigen-problem carries the
         selected outputs (_masked_ysq) -- or, wide inputs (d > 8), inside _wide_fit_ok under FGP_WIDE_FIT_DEVICE=1
-        (default off: the generic autograd loop over fgp_wide_k1 / fgp_wide_k1_bwd); GCV / CV inside _alt_loss_ok."""
+        (default off: the generic autograd loop over fgp_wide_k1 / fgp_wide_k1_bwd); GCV / CV inside _alt_loss_ok, or,
+        wide inputs, under the same switch without masks, with a scalar cv_weights and FGP_ALT_LOSS_DEVICE != 0."""
         if optimizer is not None:
             return None
         mll = loss_metric == "MLL"
-        wide_dev = (mll and self.d > _native.MAX_D and os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1"
-                    and self._wide_fit_ok())
+        wide_dev = (self.d > _native.MAX_D and os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1"
+                    and self._wide_fit_ok()
+                    and (mll or (masks is None and self._alt_loss_switch_on() and _scalar_weight(cv_weights))))
         if masks is not None:
             # only the outputs y[..., *masks] in the loss, shared hyper-parameters: the device fit on their
             # Y = sum |ytilde_b|^2 with d_out = the selected count (abstract_gp.py:220-235, 253-260)
@@ -808,8 +817,8 @@ class AbstractFastGP(torch.nn.Module):
         GP's _wide_parts_key -- so a GP's fit does not depend on whether it shares the array with a batch."""
         return self._k1parts(n)
 
-    def _wide_engine(self, iterations, lr, ysq=None, d_out=None):
-        """The WideMLL of this GP's fit (one eigen-problem)."""
+    def _wide_engine(self, iterations, lr, ysq=None, d_out=None, loss_metric="MLL", cv_weight=1.0):
+        """The WideMLL of this GP's fit (one eigen-problem), for the MLL or the GCV / CV loss."""
         from .wide_fit import WideMLL
         n = self._nh
         pb_shape, G = self._problem_batch()
@@ -819,23 +828,24 @@ class AbstractFastGP(torch.nn.Module):
         return WideMLL(self._FAMILY, self._wide_fit_parts(n), self._ysq(pb_shape, G) if ysq is None else ysq,
                        self.raw_scale.detach().reshape(1), self.raw_lengthscales.detach().reshape(1, dl),
                        self.raw_noise.detach().reshape(1), logdet_weight=d_out / G, d_out=d_out,
-                       requires_grad=self._raw_requires_grad(), lr=lr, max_iters=min(iterations + 1, 8192))
+                       requires_grad=self._raw_requires_grad(), lr=lr, max_iters=min(iterations + 1, 8192),
+                       loss_metric=loss_metric, cv_weight=cv_weight)
 
     def _alt_loss_ok(self, loss_metric, cv_weights):
         """fit(loss_metric="GCV" / "CV") on the device (fgp_nll_desc.loss_metric, ABI 16): the spectral path
         (d <= 6), one loss over at most 16 eigen-problems, a scalar cv_weights (the Parseval form of CV's
         sum_i (coeffs_i / inv_diag)^2 w needs one weight for every point); FGP_ALT_LOSS_DEVICE=0 keeps the generic
         autograd loop (A/B, tests)."""
-        if os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] == "0" or self.d > SPEC_MAX_D:
+        if not self._alt_loss_switch_on() or self.d > SPEC_MAX_D:
             return False
-        if loss_metric == "CV":
-            if torch.is_tensor(cv_weights):
-                if cv_weights.numel() != 1:
-                    return False
-            elif not np.isscalar(cv_weights):
-                return False
+        if loss_metric == "CV" and not _scalar_weight(cv_weights):
+            return False
         pb = self._problem_batch()
         return pb is not None and pb[1] <= 16 and self._spec_basis(self._nh, pb[1], force=True) is not None
+
+    @staticmethod
+    def _alt_loss_switch_on():
+        return os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
 
     def _masked_ysq(self, masks):
         """(Y [1, n], d_out) of fit(masks=...) with ONE eigen-problem (hyper-parameters shared by the outputs): Y sums
@@ -887,7 +897,7 @@ class AbstractFastGP(torch.nn.Module):
         count (distributed.fit_sharded: Y all-reduced over the ranks' output shards); loss_metric GCV / CV: the
         spectral path's alternative losses (FusedMLL)."""
         if self.d > _native.MAX_D:
-            return self._wide_engine(iterations, lr, ysq, d_out)
+            return self._wide_engine(iterations, lr, ysq, d_out, loss_metric, cv_weight)
         n = self._nh
         pb_shape, G = self._problem_batch()
         if d_out is None:

@@ -1,4 +1,4 @@
-"""Device-resident MLL fit loop of wide GPs, 9 <= d <= 64 (fgp_wide_fit_run of include/fgp_hip.h).
+"""Device-resident fit loop (MLL, GCV or CV) of wide GPs, 9 <= d <= 64 (fgp_wide_fit_run of include/fgp_hip.h).
 
 `WideMLL` is the wide counterpart of fit_engine.FusedMLL for G independent eigen-problems of size n = 2^m: the kernel
 parts ([d, n] shared by every problem, or [G, d, n]), Y[g, k] = sum over the outputs of problem g of |ytilde[k]|^2, the
@@ -23,13 +23,15 @@ def wide_mll_constant(d_out, n):
 
 class WideMLL(FitEngine):
     def __init__(self, family, parts, ysq, raw_scale, raw_lengthscales, raw_noise, logdet_weight, d_out,
-                 requires_grad=(True, True, False), lr=0.1, max_iters=1):
+                 requires_grad=(True, True, False), lr=0.1, max_iters=1, loss_metric="MLL", cv_weight=1.0):
         """
         family: 0 lattice (FFT) / 1 net (FWHT)
         parts:  [d, n] shared by the G problems, or [G, d, n]
         ysq:    [G, n]
         raw_scale [G], raw_lengthscales [G, dl] with dl in {1, d}, raw_noise [G]
         d_out:  outputs in each problem's loss (the constant 1/2 d_out n log(2 pi))
+        loss_metric: "MLL", "GCV" or "CV" (fgp_wide_fit_desc.loss_metric); cv_weight: CV's scalar weight.  The history
+                rows of GCV are (loss, numer, denom), of CV (loss, nan, nan); neither uses logdet_weight or d_out.
         """
         require_device(ysq, "WideMLL")
         self.device = ysq.device
@@ -59,6 +61,10 @@ class WideMLL(FitEngine):
         self.lr = float(lr)
         self.logdet_weight = float(logdet_weight)
         self.mll_const = wide_mll_constant(d_out, n)
+        if loss_metric not in ("MLL", "GCV", "CV"):
+            raise ValueError("loss_metric must be MLL, GCV or CV")
+        self.loss_metric = loss_metric
+        self.cv_weight = float(cv_weight)
         self._desc = N.WideFitDesc(
             family=self.family, log2n=self.m, d=d, G=self.G, parts=self.parts.data_ptr(),
             parts_stride=(d * n if self.parts.dim() == 3 else 0), ysq=self.ysq.data_ptr(), raw=self.raw.data_ptr(),
@@ -66,7 +72,8 @@ class WideMLL(FitEngine):
             logdet_weight=self.logdet_weight, mll_const=self.mll_const, rprop_prev=self.prev.data_ptr(),
             rprop_step=self.step.data_ptr(), lr=self.lr, eta_minus=RPROP_ETAS[0], eta_plus=RPROP_ETAS[1],
             step_min=RPROP_STEPS[0], step_max=RPROP_STEPS[1], loss_hist=0, raw_hist=0, grad_out=self.grad.data_ptr(),
-            work=0)
+            work=0, loss_metric={"MLL": N.LOSS_MLL, "GCV": N.LOSS_GCV, "CV": N.LOSS_CV}[loss_metric],
+            cv_weight=self.cv_weight)
         wlen = ctypes.c_int64(0)
         N.call("fgp_wide_fit_work", self._desc, ctypes.byref(wlen))
         self.work = torch.empty((wlen.value,), dtype=torch.float64, device=self.device)

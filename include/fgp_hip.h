@@ -549,6 +549,12 @@ int fgp_wide_post_mean(int family, const double* xt, int64_t N, const void* z, i
  * n_params = G (2 + dl).  loss_hist [iters][G][3] = (loss, norm term, w logdet); raw_hist [iters][n_params]; row i of
  * both holds the loss and the parameters AT iteration i, before its step.  grad_out [n_params]: the raw-parameter
  * gradient of the last evaluation.  ysq and work must be 16-byte aligned.
+ * loss_metric FGP_LOSS_GCV / FGP_LOSS_CV (AbstractGP.fit's alternative losses, abstract_gp.py:242-273; one task, the
+ * eigenvalues real as above): with N1 = sum Y / ev^2 and lambda' = ev - noise,
+ *   GCV  T = sum 1 / ev,      D = (T / n)^2, loss = N1 / D,       loss_hist row (loss, N1, D)
+ *   CV   T = sum 1 / lambda', I = T / n,     loss = w N1 / I^2,   loss_hist row (loss, NaN, NaN),  w = cv_weight
+ * The eigenvalue-terms stage is then two kernels (the partial sums; g~, which needs the problem's N1 and T), ten
+ * launches per iteration; logdet_weight and mll_const are not used, and work is longer by the extra partials.
  * (The two functions are declared `extern`: tests/test_wide_cpu.py takes the plain `int fgp_wide_*` declarations
  * as the ABI 19 set it calls one by one.) */
 typedef struct fgp_wide_fit_desc {
@@ -573,14 +579,17 @@ typedef struct fgp_wide_fit_desc {
   double* raw_hist;
   double* grad_out;
   void* work;                 /* fgp_wide_fit_work doubles */
+  int loss_metric;            /* FGP_LOSS_MLL (0: a zeroed field is the MLL) / FGP_LOSS_GCV / FGP_LOSS_CV */
+  double cv_weight;           /* CV: the scalar weight w of loss = w N1 / I^2 (finite); else unused */
 } fgp_wide_fit_desc;
 
 /* Doubles of `work`.  Validates the desc's sizes (not its pointers) as fgp_wide_fit_run does. */
 extern int fgp_wide_fit_work(const fgp_wide_fit_desc* desc, int64_t* len);
 /* Iterations iter0 .. iter0 + iters - 1 (history rows), with the semantics of fgp_fit_run: final_no_update leaves the
  * last evaluated parameters unstepped.  Arguments are validated before any HIP call (also without a device):
- * d outside 9 .. 64, log2n outside 0 .. 24, G < 1, dl not in {1, d}, a null pointer and negative iters each return
- * FGP_ERR_INVALID with a message that names the field. */
+ * d outside 9 .. 64, log2n outside 0 .. 24, G < 1, dl not in {1, d}, a loss_metric outside the three, a non-finite
+ * cv_weight under FGP_LOSS_CV, a null pointer and negative iters each return FGP_ERR_INVALID with a message that
+ * names the field. */
 extern int fgp_wide_fit_run(const fgp_wide_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
 
 

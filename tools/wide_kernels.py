@@ -9,6 +9,8 @@
                                              # autograd loop alternating in one process, 5 repetitions each and their
                                              # medians; one JSON line
     python tools/wide_kernels.py --fit-trace [m]   # one 20-iteration device-loop fit only (launches per iteration)
+    --metric MLL|GCV|CV                      # with --fit / --fit-trace: the loss of the fit (default MLL; CV with
+                                             # cv_weights = 0.5); the JSON line names it and the last loss of each loop
 
 d = 16, n = 2^m, m = 16 by default (lattice, alpha = 2, lengthscales linspace(0.05, 0.3, d)), one hyper-parameter row; post_mean at
 N = 4096 test points, one output.  Byte / operation models:
@@ -58,17 +60,21 @@ def timed(fn, reps):
 
 
 FIT_ITERS = 20
+METRIC = "MLL"
 
 
 def fit_once(gp, raw0, device_loop):
-    """One 20-iteration MLL fit from the parameters raw0 (no early stop), by the device loop or the generic one."""
+    """One 20-iteration fit of the loss METRIC from the parameters raw0 (no early stop), by the device loop or the
+    generic one."""
     os.environ["FGP_WIDE_FIT_DEVICE"] = "1" if device_loop else "0"
     for name, val in raw0.items():
         old = gp._parameters[name]
         gp._parameters[name] = torch.nn.Parameter(val.clone(), requires_grad=old.requires_grad)
     gp._cache = {k: v for k, v in gp._cache.items() if not k[2]}
     gp._snap = None
-    return gp.fit(iterations=FIT_ITERS, verbose=0, stop_crit_wait_iterations=FIT_ITERS + 5)
+    kw = dict(cv_weights=0.5) if METRIC == "CV" else {}
+    return gp.fit(loss_metric=METRIC, iterations=FIT_ITERS, verbose=0, stop_crit_wait_iterations=FIT_ITERS + 5,
+                  store_loss_hist=True, **kw)
 
 
 def fit_mode(trace):
@@ -78,9 +84,10 @@ def fit_mode(trace):
         fit_once(gp, raw0, True)
         torch.cuda.synchronize()
         return
-    res = {"d": D, "n": 2 ** M, "iterations": FIT_ITERS, "ms_per_iteration": {"device": [], "generic": []}}
-    for dev in (True, False):
-        fit_once(gp, raw0, dev)
+    res = {"d": D, "n": 2 ** M, "metric": METRIC, "iterations": FIT_ITERS,
+           "ms_per_iteration": {"device": [], "generic": []}, "last_loss": {}}
+    for key, dev in (("device", True), ("generic", False)):
+        res["last_loss"][key] = float(fit_once(gp, raw0, dev)["loss_hist"][-1])
     for _ in range(5):                      # alternate the two loops in one process
         for key, dev in (("device", True), ("generic", False)):
             ms = timed(lambda: fit_once(gp, raw0, dev), 1)
@@ -90,9 +97,15 @@ def fit_mode(trace):
 
 
 def main():
-    global M
-    mode = sys.argv[1] if len(sys.argv) > 1 else "time"
-    M = int(sys.argv[2]) if len(sys.argv) > 2 else M
+    global M, METRIC
+    argv = list(sys.argv)
+    if "--metric" in argv:
+        i = argv.index("--metric")
+        METRIC = argv[i + 1].upper()
+        assert METRIC in ("MLL", "GCV", "CV"), "--metric MLL|GCV|CV"
+        del argv[i:i + 2]
+    mode = argv[1] if len(argv) > 1 else "time"
+    M = int(argv[2]) if len(argv) > 2 else M
     if mode in ("--fit", "--fit-trace"):
         return fit_mode(mode == "--fit-trace")
     gp = make()
