@@ -208,6 +208,9 @@ _SIGNATURES = {
     # addition to ABI 20: the device-resident wide fit loop
     "fgp_wide_fit_work": [_P_WIDEFIT, _c_pl],
     "fgp_wide_fit_run": [_P_WIDEFIT, _c_int, _c_int, _c_int, _c_vp],
+    # addition to ABI 20: the posterior variance's quadratic form for wide d
+    "fgp_wide_post_var_qf": [_c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd, _c_vp,
+                             _c_i64, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp],
 }
 
 

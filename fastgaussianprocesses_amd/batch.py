@@ -12,7 +12,8 @@ parameters are restored, and the GP objects hold the fitted parameters and data 
 
 Wide GPs (9 <= d <= 64) are fitted by fgp_wide_fit_run (wide_fit.WideMLL: the same per-problem loop, the parts
 shared when every GP has the same generating vector / matrices) and predicted with one fgp_wide_post_mean per GP
-and each GP's own post_var: fgp_pred_desc and the batched prediction kernels are d <= 8.
+and (below n = 2^13) each GP's own post_var: fgp_pred_desc and the batched prediction kernels are d <= 8; from
+n = 2^13 post_var is one fgp_wide_post_var_qf call per chunk of test points over all GPs.
 """
 import collections
 import ctypes
@@ -521,12 +522,24 @@ class GPBatch(object):
 
     def post_var(self, x, chunk=16):
         """[P, N] posterior variances at the GPs' current n (AbstractGP.post_var, abstract_gp.py:381-416)."""
-        if self.m < 13 or self.d > N.MAX_D:     # (wide GPs: no batched prediction kernel)
+        wide = self.d > N.MAX_D
+        if self.m < 13 or (wide and not ops.wide_post_var_qf()):
             x = torch.as_tensor(x)
             return torch.stack([gp.post_var(x if x.ndim == 2 else x[p]) for p, gp in enumerate(self.gps)])
         self.coeffs()
         x, xs, Nt = self._points(x)
         out = torch.empty((self.P, Nt), dtype=torch.float64, device=self.device)
+        if wide:
+            # wide GPs (fgp_pred_desc is FGP_MAX_D-sized): the P quadratic forms of a chunk of test points in one
+            # fgp_wide_post_var_qf call, K(x, x) = scale prod_j (1 + l_j part0_j) from the hyp rows
+            hyp, wa = self._hyp(), self._st["wa"]
+            part0 = torch.tensor(self.part0, dtype=torch.float64, device=self.device)
+            kxx = hyp[:, :1] * (1 + hyp[:, 1:] * part0).prod(-1, keepdim=True)
+            for t0 in range(0, Nt, chunk):
+                qf = ops.wide_post_var_quadform(self.family, x[..., t0:t0 + chunk, :], self.z, hyp, wa,
+                                                alphas=self.gps[0]._alphas, tbits=self.tbits)
+                out[:, t0:t0 + chunk] = (kxx - qf).clamp_(min=0)
+            return out
         cdt = torch.complex128 if self.family == ops.LATTICE else torch.float64
         desc = self._desc()
         part0 = N.double_array(self.part0)

@@ -18,6 +18,7 @@
 #include "fgp_common.h"
 #include "fgp_factors.h"
 #include "fgp_runtime.h"
+#include "fgp_wide.h"
 #include "../../include/fgp_hip.h"
 
 namespace fgp {
@@ -929,6 +930,212 @@ static int launch_qf(const Switches& sw, int family, const double* xt, int64_t N
     return check_launch("k_qf_cols");
   }), "k_qf_cols", m1);
 }
+
+// ---------------------------------------------------------------- wide inputs (9 <= d <= FGP_WIDE_MAX_D)
+// The row pass of the quadratic form for wide d: k_qf_rows' geometry (one workgroup = one 4096-point tile of one
+// (problem, test point) row of work, 16 kernel values per thread at e = 2 tid + 512 kk, the same LDS transform tail
+// and twiddled store) around a factor loop over a run-time d: the dimension loop is outermost, the test point's
+// per-dimension constants (coordinate -- nets: its t-bit integer --, fa, fc, order) sit in LDS and are read
+// uniformly, the 8 16-byte loads of z row j + 1 are in flight while row j's 16 factors are evaluated, and no
+// per-thread array is indexed by j.  A kernel value is formed as k_wide_rows (fgp_wide.hip) forms it -- the product
+// over j ascending from 1.0, times the scale last -- so the transformed row has the bits of fgp_wide_kernel_rows' row.
+// ORD = 4: every dimension of Bernoulli order 4 (alpha = 2); 0: per-dimension orders (and nets).
+// The column pass is k_qf_cols, which reads log2n, N, work, wa, partial and the wa stride only.
+//
+// Grid order: consecutive workgroups are the (problem, test point) rows of ONE tile (FGP_WIDE_QF_TILE_MAJOR = 1), so
+// the rows of a call share the tile's z (32 KB d) while it is cached; 0 = k_qf_rows' order (a row's tiles in turn),
+// kept for A/B builds.  The results are identical.
+#ifndef FGP_WIDE_QF_TILE_MAJOR
+#define FGP_WIDE_QF_TILE_MAJOR 1
+#endif
+
+struct WideQfArgs {
+  int log2n, d, tbits, N, P;
+  const double* xt;          // [P][N][d]
+  const void* z;             // [P][d][n] float64 (lattice) / int64 (net)
+  WideSpec spec;
+  const double* hyp;         // device [P][1 + d]: scale, lengthscales
+  void* work;                // [P][N][n]
+  ProbStrides ps;            // per-problem strides of xt, z, hyp (0: shared)
+};
+
+template <int P2, typename T, int ORD>
+__global__ __launch_bounds__(kWG) void k_wide_qf_rows(WideQfArgs q, const double2* __restrict__ tw,
+                                                      const double2* __restrict__ twm) {
+  constexpr int N2 = 1 << P2, TL = N2 / 16, RPW = kTile / N2;
+  constexpr int FAM = sizeof(T) == 16 ? 0 : 1;
+  using Z2 = std::conditional_t<FAM == 0, double2, longlong2>;
+  __shared__ T lds[kTile + kTile / 16];
+  __shared__ T red[kWG / 64];
+  __shared__ double xs[kWD], fa_s[kWD], fc_s[kWD];
+  __shared__ int ord_s[kWD];
+  const int m = q.log2n, m1 = m - P2;
+  const int64_t n = (int64_t)1 << m;
+  const unsigned tiles = (unsigned)(n >> kTileLog), rows = (unsigned)q.P * (unsigned)q.N;
+#if FGP_WIDE_QF_TILE_MAJOR
+  const int tg = (int)(blockIdx.x % rows);            // (problem, test point) row of work
+  const int row0 = (int)(blockIdx.x / rows) * RPW;
+#else
+  const int tg = (int)(blockIdx.x / tiles);
+  const int row0 = (int)(blockIdx.x % tiles) * RPW;
+  (void)rows;
+#endif
+  (void)tiles;
+  const int pb = tg / q.N, t = tg % q.N;
+  const int tid = threadIdx.x;
+  const double* hyp = q.hyp + pb * q.ps.h;
+  if (tid < q.d) {
+    const int j = tid;
+    const double v = q.xt[pb * q.ps.x + (int64_t)t * q.d + j];
+    const double l = hyp[1 + j];
+    const int ord = ORD ? ORD : q.spec.order[j];
+    ord_s[j] = ord;
+    if constexpr (FAM == 0) {
+      const double a = l * q.spec.coef[j];
+      xs[j] = v;
+      fa_s[j] = a;
+      fc_s[j] = fac_const(ord, a);
+    } else {
+      xs[j] = __longlong_as_double((long long)to_bits(v, q.tbits));
+      fa_s[j] = net_fa(ord, l);
+      fc_s[j] = 3.0 * l;
+    }
+  }
+  __syncthreads();
+  const double scale = hyp[0];
+  const int64_t base = (int64_t)row0 * N2;
+  // z row j of this thread: elements base + 2 tid + 512 kk (+ 1), 8 bytes each in both families
+  const double* zt = static_cast<const double*>(q.z) + pb * q.ps.z + base + 2 * tid;
+  double kv0[8], kv1[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) kv0[kk] = kv1[kk] = 1.0;
+  Z2 zn[8];
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) zn[kk] = *reinterpret_cast<const Z2*>(zt + 512 * kk);
+  for (int j = 0; j < q.d; ++j) {
+    Z2 zv[8];
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) zv[kk] = zn[kk];
+    if (j + 1 < q.d) {
+      const double* zr = zt + (int64_t)(j + 1) * n;
+#pragma unroll
+      for (int kk = 0; kk < 8; ++kk) zn[kk] = *reinterpret_cast<const Z2*>(zr + 512 * kk);
+    }
+    const double xj = xs[j], a = fa_s[j], c = fc_s[j];
+    const int ord = ORD ? ORD : ord_s[j];
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      if constexpr (FAM == 0) {
+        kv0[kk] *= lat_factor(ord, fabs(xj - zv[kk].x), a, c);
+        kv1[kk] *= lat_factor(ord, fabs(xj - zv[kk].y), a, c);
+      } else {
+        const unsigned long long xb = (unsigned long long)__double_as_longlong(xj);
+        kv0[kk] *= net_factor_o(ord, xb ^ (unsigned long long)zv[kk].x, q.tbits, a, c);
+        kv1[kk] *= net_factor_o(ord, xb ^ (unsigned long long)zv[kk].y, q.tbits, a, c);
+      }
+    }
+  }
+  double sum = 0.0;
+#pragma unroll
+  for (int kk = 0; kk < 8; ++kk) {
+    kv0[kk] = scale * kv0[kk];
+    kv1[kk] = scale * kv1[kk];
+    sum += kv0[kk] + kv1[kk];
+  }
+  // from here on: k_qf_rows' tail
+  if constexpr (RPW == 1) {
+    const double mean = block_sum(sum, (double*)red) * (1.0 / N2);
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      const int e = 2 * tid + 512 * kk;
+      if constexpr (FAM == 0) {
+        lds[padi(e)] = make_double2(kv0[kk] - mean, 0.0);
+        lds[padi(e + 1)] = make_double2(kv1[kk] - mean, 0.0);
+      } else {
+        lds[padi(e)] = kv0[kk] - mean;
+        lds[padi(e + 1)] = kv1[kk] - mean;
+      }
+    }
+    __syncthreads();
+    T mt;
+    if constexpr (FAM == 0) mt = make_double2(mean, 0.0);
+    else mt = mean;
+    transform_add_mean<P2, false>(lds, tid, mt, tw);
+  } else {
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+      const int e = 2 * tid + 512 * kk;
+      if constexpr (FAM == 0) {
+        lds[padi(e)] = make_double2(kv0[kk], 0.0);
+        lds[padi(e + 1)] = make_double2(kv1[kk], 0.0);
+      } else {
+        lds[padi(e)] = kv0[kk];
+        lds[padi(e + 1)] = kv1[kk];
+      }
+    }
+    __syncthreads();
+    T* s = lds + (tid / TL) * (N2 + N2 / 16);
+    center_transform<P2, false>(s, tid % TL, 1, red, tw);
+  }
+  T* out = static_cast<T*>(q.work) + (int64_t)tg * n + base;
+  if constexpr (FAM == 0 && RPW == 1) {
+    const RowTwiddle rt((unsigned)row0, tid, P2, m1, tw, twm);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int e = tid + k * kWG;
+      out[e] = cmul(lds[padi(e)], rt.at(k, P2, m1, tw, twm));
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      const int e = tid + k * kWG;
+      T v = lds[padi(e)];
+      if constexpr (FAM == 0) {
+        const unsigned ex = brev_bits((unsigned)(row0 + (e >> P2)), m1) * (unsigned)(e & (N2 - 1));
+        v = cmul(v, inter_tw(ex, P2, m1, tw, twm));
+      }
+      out[e] = v;
+    }
+  }
+}
+
+// quadratic-form partials of P problems x N test points of wide d (k_wide_qf_rows + k_qf_cols), full length
+static int launch_wide_qf(const WideQfArgs& a, int family, const double* wa, int64_t wa_stride, double* partial,
+                          hipStream_t st) {
+  const Tables* tb = get_tables(st);
+  if (!tb) return set_error(kErrHip, "twiddle table initialisation failed");
+  const int log2n = a.log2n;
+  const int m2 = split_m2(log2n), m1 = log2n - m2;
+  const dim3 grid((unsigned)(((int64_t)a.P * a.N) << (log2n - kTileLog)));
+  const double2* tw = tb->tw4096;
+  const double2* twm = tb->twm[log2n];
+  const bool lat = family == FGP_FAMILY_LATTICE;
+  bool uniform4 = lat;
+  for (int j = 0; j < a.d; ++j) uniform4 = uniform4 && a.spec.order[j] == 4;
+  int rc = no_kernel(dispatch_range<9, 12>(m2, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (!lat) k_wide_qf_rows<PP, double, 0><<<grid, kWG, 0, st>>>(a, tw, twm);
+    else if (uniform4) k_wide_qf_rows<PP, double2, 4><<<grid, kWG, 0, st>>>(a, tw, twm);
+    else k_wide_qf_rows<PP, double2, 0><<<grid, kWG, 0, st>>>(a, tw, twm);
+    return check_launch("k_wide_qf_rows");
+  }), "k_wide_qf_rows", m2);
+  if (rc != kOk) return rc;
+  QfArgs q{};              // what k_qf_cols reads: log2n, N, work, wa, partial and the wa stride
+  q.log2n = log2n;
+  q.d = a.d;
+  q.tbits = a.tbits;
+  q.N = a.N;
+  q.wa = wa;
+  q.work = a.work;
+  q.partial = partial;
+  q.ps = ProbStrides{0, 0, 0, wa_stride};
+  return no_kernel(dispatch_range<4, 12>(m1, [&](auto pc) {
+    constexpr int PP = decltype(pc)::value;
+    if (lat) k_qf_cols<PP, double2><<<grid, kWG, 0, st>>>(q, tw);
+    else k_qf_cols<PP, double><<<grid, kWG, 0, st>>>(q, tw);
+    return check_launch("k_qf_cols");
+  }), "k_qf_cols", m1);
+}
 }  // namespace fgp
 
 extern "C" {
@@ -1019,6 +1226,44 @@ int fgp_post_var_batched(const fgp_pred_desc* pd, const double* xt, int64_t xt_s
   k_qf_finish<<<(unsigned)((int64_t)pd->P * N), kWG, 0, st>>>(partial, qf_partials(sw, pd->family, log2n), pd->hyp,
                                                                pd->hyp_stride, p0, d, N, out);
   return check_launch("k_qf_finish");
+}
+
+int fgp_wide_post_var_qf(int family, const double* xt, int64_t xt_stride, int64_t N, const void* z, int64_t z_stride,
+                         int log2n, int d, int tbits, const int* order, const double* coef, const double* hyp,
+                         int64_t hyp_stride, const double* wa, int64_t wa_stride, int P, void* work, double* partial,
+                         double* out, void* stream) {
+  const char* fn = "fgp_wide_post_var_qf";
+  int rc = wide_d_ok(fn, d);
+  if (rc != kOk) return rc;
+  if (N < 0 || log2n < 13 || log2n > kMaxLog2N || P < 1 || P > 65535 || xt_stride < 0 || z_stride < 0 || hyp_stride < 0 ||
+      wa_stride < 0)
+    return set_error(kErrInvalid, "%s: needs 13 <= log2n <= 24, N >= 0, 1 <= P <= 65535 and strides >= 0 (log2n=%d N=%lld P=%d)",
+                     fn, log2n, (long long)N, P);
+  if (N == 0) return kOk;
+  if (!xt || !z || !hyp || !wa || !work || !partial || !out) return set_error(kErrInvalid, "%s: null pointer", fn);
+  WideQfArgs a;
+  rc = wide_spec(fn, family, d, order, coef, a.spec);
+  if (rc != kOk) return rc;
+  if (N >= ((int64_t)1 << 31) || (((int64_t)P * N) << (log2n - kTileLog)) >= ((int64_t)1 << 31))
+    return set_error(kErrUnsupported, "%s: P * N too large", fn);
+  // the row pass reads z in 16-byte pairs and writes whole elements of work
+  if ((reinterpret_cast<uintptr_t>(z) & 15) || (z_stride & 1) || (reinterpret_cast<uintptr_t>(work) & 15))
+    return set_error(kErrInvalid, "%s: z and work must be 16-byte aligned (z_stride even)", fn);
+  a.log2n = log2n;
+  a.d = d;
+  a.tbits = tbits;
+  a.N = (int)N;
+  a.P = P;
+  a.xt = xt;
+  a.z = z;
+  a.hyp = hyp;
+  a.work = work;
+  a.ps = ProbStrides{xt_stride, z_stride, hyp_stride, wa_stride};
+  hipStream_t st = (hipStream_t)stream;
+  rc = launch_wide_qf(a, family, wa, wa_stride, partial, st);
+  if (rc != kOk) return rc;
+  k_sum_chunks<<<(unsigned)((int64_t)P * N), kWG, 0, st>>>(partial, (int64_t)1 << (log2n - kTileLog), out, N, N);
+  return check_launch("k_sum_chunks");
 }
 
 int fgp_inv_eig(int family, const void* lam, const void* ytilde, int64_t yt_stride, const double* raw_noise,

@@ -22,20 +22,15 @@
 #include "fgp_common.h"
 #include "fgp_factors.h"
 #include "fgp_runtime.h"
+#include "fgp_wide.h"
 #include "../../include/fgp_hip.h"
 
 namespace fgp {
 
-constexpr int kWD = FGP_WIDE_MAX_D;   // per-dimension table length
 constexpr int kWPmB = 4;              // outputs per post_mean kernel evaluation (as fgp_post_mean)
 constexpr int kWSlab = 64;            // training points per LDS slab of k_wide_post_mean (64 dims x 64 points = 32 KB)
 constexpr int kWIB = 8;               // training points whose products a thread holds at once
 constexpr int kWRowsG = 4;            // hyper-parameter rows per k_wide_k1 / k_wide_rows workgroup
-
-struct WideSpec {
-  int order[kWD];
-  double coef[kWD];
-};
 
 struct WideGen {
   unsigned z[kWD];   // z_j mod 2^bits
@@ -428,34 +423,7 @@ __global__ __launch_bounds__(kWG) void k_wide_post_mean(const double* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int wide_d_ok(const char* fn, int d) {
-  if (d <= FGP_MAX_D || d > FGP_WIDE_MAX_D)
-    return set_error(kErrInvalid, "%s: d=%d outside %d..%d (d <= %d: the entry point without _wide)", fn, d,
-                     FGP_MAX_D + 1, FGP_WIDE_MAX_D, FGP_MAX_D);
-  return kOk;
-}
-
-// Lattice: Bernoulli order 2 alpha and coefficient per dimension.  Net: Walsh order per dimension (1..4; order =
-// NULL or 0 entries: 1), coefficients unused.
-static int wide_spec(const char* fn, int family, int d, const int* order, const double* coef, WideSpec& spec) {
-  if (family != FGP_FAMILY_LATTICE && family != FGP_FAMILY_NET) return set_error(kErrInvalid, "%s: bad family %d", fn, family);
-  const bool lat = family == FGP_FAMILY_LATTICE;
-  if (lat && (!order || !coef)) return set_error(kErrInvalid, "%s: null pointer", fn);
-  for (int j = 0; j < kWD; ++j) {
-    if (lat) {
-      spec.order[j] = j < d ? order[j] : 0;
-      spec.coef[j] = j < d ? coef[j] : 0.0;
-      if (j < d && (order[j] < 2 || order[j] > 8 || (order[j] & 1)))
-        return set_error(kErrUnsupported, "%s: Bernoulli order %d unsupported", fn, order[j]);
-    } else {
-      spec.order[j] = (order && j < d && order[j] > 0) ? order[j] : 1;
-      spec.coef[j] = 0.0;
-      if (spec.order[j] > 4) return set_error(kErrUnsupported, "%s: Walsh order %d unsupported", fn, spec.order[j]);
-    }
-  }
-  return kOk;
-}
-
+// (kWD, WideSpec, wide_d_ok and wide_spec: fgp_wide.h)
 template <int FAM>
 static int wide_post_mean_launch(const double* xT, int64_t N, const void* z, int64_t n, int d, const WideSpec& spec,
                                  int tbits, const double* hyp, int Gk, const double* coeffs, int64_t cstride, int B,

@@ -11,7 +11,8 @@ misuse.  Every numerical hot spot runs in the HIP library (include/fgp_hip.h):
                                back in chunks to apply the reference's early-stopping rule exactly
                                (9 <= d <= 64: fgp_wide_fit_run under FGP_WIDE_FIT_DEVICE=1, else the generic loop)
   post_mean                 -> fgp_post_mean (matrix-free cross-kernel contraction)
-  post_var / post_cov       -> fgp_kernel_rows + the transform solve
+  post_var / post_cov       -> fgp_kernel_rows + the transform solve (post_var at n > 4096: the Parseval quadratic
+                               form, fgp_post_var_qf / fgp_wide_post_var_qf)
 
 This module holds single-task GPs (num_tasks=None or 1) without derivative information
 (beta = kappa = 0); multitask (num_tasks > 1) and derivative-informed GPs are built by the same
@@ -1166,9 +1167,31 @@ class AbstractFastGP(torch.nn.Module):
         out = torch.empty(x.size(0), dtype=torch.float64, device=self.device)
         for t0 in range(0, x.size(0), chunk):
             xs = x[t0:t0 + chunk].contiguous()
-            out[t0:t0 + xs.size(0)] = ops.post_var_quadform(self._FAMILY, xs, z, hyp, wa, alphas=self._alphas,
-                                                            tbits=self._tbits())
+            if self.d > _native.MAX_D:
+                out[t0:t0 + xs.size(0)] = ops.wide_post_var_quadform(self._FAMILY, xs, z, hyp, wa, alphas=self._alphas,
+                                                                     tbits=self._tbits())[0]
+            else:
+                out[t0:t0 + xs.size(0)] = ops.post_var_quadform(self._FAMILY, xs, z, hyp, wa, alphas=self._alphas,
+                                                                tbits=self._tbits())
         return out
+
+    def _wide_post_var_problems(self, x, n, work_bytes=1 << 30):
+        """_post_var_problems' quadratic forms for d > 8: the G eigen-problems on one point set as the problems of
+        fgp_wide_post_var_qf (z stride 0), in chunks of <= work_bytes scratch -> [*shape_batch, N]."""
+        pb, G = self._problem_batch()
+        wa = self._cached(("inv_real", n), lambda: (lambda a: (a.real if a.is_complex() else a))(self._inv(n)))
+        wa = wa.expand(tuple(pb) + (n,)).reshape(G, n).contiguous()
+        hyp = self._hyp_rows(True).contiguous()                   # [G, 1 + d]
+        z = self._points_T(n)
+        x = x.contiguous()
+        Nt = x.size(0)
+        per = Nt * n * (16 if self._FAMILY == ops.LATTICE else 8)
+        pc = max(1, min(G, work_bytes // per))
+        out = torch.empty((G, Nt), dtype=torch.float64, device=self.device)
+        for p0 in range(0, G, pc):
+            out[p0:p0 + pc] = ops.wide_post_var_quadform(self._FAMILY, x, z, hyp[p0:p0 + pc], wa[p0:p0 + pc],
+                                                         alphas=self._alphas, tbits=self._tbits())
+        return out.reshape(tuple(self.shape_batch) + (Nt,))
 
     def _post_var_problems(self, x, n, work_bytes=1 << 30):
         """Per-problem hyper-parameters (G eigen-problems on one point set, e.g. C5 per-output): every
@@ -1298,10 +1321,18 @@ class AbstractFastGP(torch.nn.Module):
             self._defer_unit(x)
             bp = self._has_batch_params()
             qf_ok = not self._gradmode() and 4096 < n <= 2 ** 24 and self.d <= 8 and self._lam_fusable(n)
+            # d > 8: the same quadratic form by fgp_wide_post_var_qf; wa = Re(_inv(n)) whatever the parameter transforms
+            wide_ok = (not self._gradmode() and 4096 < n <= 2 ** 24 and self.d > _native.MAX_D
+                       and ops.wide_post_var_qf())
+            pbw = self._problem_batch() if (wide_ok and bp and not self.adaptive_nugget) else None
             if qf_ok and not bp:
                 diag = self._kdiag(x) - self._post_var_qf(x, n)
             elif qf_ok and not self.adaptive_nugget and tuple(self._problem_batch()[0]) == tuple(self.shape_batch):
                 diag = self._post_var_problems(x, n)
+            elif wide_ok and not bp and self._inv(n).numel() == n:
+                diag = self._kdiag(x) - self._post_var_qf(x, n)
+            elif pbw is not None and tuple(pbw[0]) == tuple(self.shape_batch):
+                diag = self._kdiag(x) - self._wide_post_var_problems(x, n)
             else:
                 rows = self._cross_rows(x, n, bp)                      # [Gk, N, n]
                 kmat = rows[0] if not bp else rows.reshape(tuple(self.shape_batch) + rows.shape[1:])

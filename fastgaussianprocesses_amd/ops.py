@@ -621,6 +621,39 @@ def post_var_quadform(family, xt, z_dn, hyp, wa, alphas=None, tbits=0):
     return out
 
 
+def wide_post_var_qf():
+    """FGP_WIDE_POST_VAR_QF=0 keeps the kernel rows and the transform solve for post_var at d > 8 (A/B runs, tests);
+    default: the Parseval quadratic form, fgp_wide_post_var_qf."""
+    return os.environ.get("FGP_WIDE_POST_VAR_QF", "1")[:1] != "0"
+
+
+def wide_post_var_quadform(family, xt, z, hyp, wa, alphas=None, tbits=0):
+    """q[p, t] = sum_k wa_p[k] |ft(K_p(xt_p[t], z_p))_k|^2 -> [P, N] (fgp_wide_post_var_qf), 9 <= d <= 64, n = 2^13..2^24.
+
+    xt [N, d] (shared) or [P, N, d]; z [d, n] (shared) or [P, d, n] (float64 lattice / int64 net); hyp device [P, 1 + d]
+    (scale, lengthscales) or [1 + d] (shared); wa [P, n] or [n] (shared).  P is the leading size of whichever is
+    stacked."""
+    require_device(xt, "wide_post_var_quadform")
+    xt = xt.to(torch.float64).contiguous()
+    hyp = hyp.to(torch.float64).contiguous()
+    z, wa = z.contiguous(), wa.to(torch.float64).contiguous()
+    Nt, d = xt.shape[-2:]
+    n = z.shape[-1]
+    m = log2_exact(n)
+    stacked = [a.shape[0] for a, nd in ((xt, 3), (z, 3), (hyp, 2), (wa, 2)) if a.dim() == nd]
+    P = stacked[0] if stacked else 1
+    assert all(s == P for s in stacked) and z.shape[-2] == d and hyp.shape[-1] == 1 + d and wa.shape[-1] == n
+    cdt = torch.complex128 if family == LATTICE else torch.float64
+    work = torch.empty((P, Nt, n), dtype=cdt, device=xt.device)
+    partial = torch.empty((P, Nt, n >> 12), dtype=torch.float64, device=xt.device)
+    out = torch.empty((P, Nt), dtype=torch.float64, device=xt.device)
+    order, coef = _pred_args(family, alphas, d)
+    N.call("fgp_wide_post_var_qf", family, N.ptr(xt), Nt * d if xt.dim() == 3 else 0, Nt, N.ptr(z),
+           d * n if z.dim() == 3 else 0, m, d, int(tbits), order, coef, N.ptr(hyp), 1 + d if hyp.dim() == 2 else 0,
+           N.ptr(wa), n if wa.dim() == 2 else 0, P, N.ptr(work), N.ptr(partial), N.ptr(out), _stream(xt))
+    return out
+
+
 def double_update(family, prev, nxt):
     """ft of 2n values from ft of the first n (prev [..., n]) and of the next n (nxt [..., n]): one DIT
     stage (fgp_double_update; _LamCaches / _YtildeCache doubling, util.py:113-132,173-178)."""

@@ -592,6 +592,23 @@ extern int fgp_wide_fit_work(const fgp_wide_fit_desc* desc, int64_t* len);
  * names the field. */
 extern int fgp_wide_fit_run(const fgp_wide_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
 
+/* Addition to ABI 20 -- fgp_post_var_qf / the quadratic form of fgp_post_var_batched for wide d:
+ *   out[p, t] = sum_k wa_p[k] |ft(K_p(xt_p[t], z_p))_k|^2   for 9 <= d <= 64, 13 <= log2n <= 24,
+ * P problems x N test points in two launches plus the sum of the n/4096 partials per (problem, test point): the
+ * kernel row is generated inside the transform's row pass with the arithmetic of fgp_wide_kernel_rows (the same bits),
+ * the column pass is fgp_post_var_qf's.  Always the full-length transform (FGP_R2C is not consulted).
+ * xt [P][N][d], z [P][d][n] (float64 lattice / int64 net), hyp device [P][1 + d] (scale, lengthscales), wa [P][n]:
+ * *_stride = elements between consecutive problems, 0 = shared.  order / coef host [d] as fgp_wide_kernel_rows.
+ * work: [P][N][n] complex128 (lattice) / float64 (net), 16-byte aligned; partial: [P][N][n/4096]; out: [P][N], the
+ * quadratic form itself (the caller subtracts it from K(x, x) and clamps at 0).
+ * Validated before any HIP call (also without a device): d outside 9 .. 64, log2n outside 13 .. 24, N < 0 (N = 0
+ * returns FGP_OK), P outside 1 .. 65535, a negative stride, a null pointer, a bad family: FGP_ERR_INVALID; a bad order
+ * or P N 2^(log2n - 12) >= 2^31: FGP_ERR_UNSUPPORTED.  (`extern` as the fit entry points above.) */
+extern int fgp_wide_post_var_qf(int family, const double* xt, int64_t xt_stride, int64_t N, const void* z,
+                                int64_t z_stride, int log2n, int d, int tbits, const int* order, const double* coef,
+                                const double* hyp, int64_t hyp_stride, const double* wa, int64_t wa_stride, int P,
+                                void* work, double* partial, double* out, void* stream);
+
 
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):
  * xb[i - n_min][j] = XOR_{k: bit k of i} C[j][k] XOR shift[j] (t-bit ints), x = xb 2^-t; C [d][mcols] and

@@ -12,6 +12,15 @@
     --metric MLL|GCV|CV                      # with --fit / --fit-trace: the loss of the fit (default MLL; CV with
                                              # cv_weights = 0.5); the JSON line names it and the last loss of each loop
 
+    python tools/wide_kernels.py --post-var [m]    # ms per post_var of 64 test points: the Parseval quadratic form
+                                             # (fgp_wide_post_var_qf, "qf") and rows-and-solve (FGP_WIDE_POST_VAR_QF=0,
+                                             # "rows") in one process, alternating qf - rows - qf per repetition, medians
+                                             # of 5, each timing ended by a synchronise after a warm-up of both paths;
+                                             # the spread of the two qf series (A - A) and the peak allocation of both
+                                             # paths; one JSON line
+    --d D / --family lattice|net             # with --post-var: the dimension (default 16) and the family (net: alpha = 1,
+                                             # unit-upper-triangular matrices; d = 64: lengthscales linspace(0.01, 0.05))
+
 d = 16, n = 2^m, m = 16 by default (lattice, alpha = 2, lengthscales linspace(0.05, 0.3, d)), one hyper-parameter row; post_mean at
 N = 4096 test points, one output.  Byte / operation models:
     k_wide_k1       8 d n + 8 n        bytes
@@ -96,9 +105,70 @@ def fit_mode(trace):
     print(json.dumps(res))
 
 
+def net_matrices(d, seed, t=32, mcols=32):
+    """Unit-upper-triangular generating matrices (column k: bit t-1-k plus random more significant bits)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    C = np.zeros((d, mcols), dtype=np.uint64)
+    for j in range(d):
+        for k in range(mcols):
+            hi = int(rng.integers(0, 1 << k)) if k > 0 else 0
+            C[j, k] = np.uint64((1 << (t - 1 - k)) | (hi << (t - k)))
+    return C
+
+
+PV_N = 64
+
+
+def post_var_mode(family):
+    torch.set_default_dtype(torch.float64)
+    ls = torch.linspace(0.01, 0.05, D) if D == 64 else torch.linspace(0.05, 0.3, D)
+    if family == "lattice":
+        gp = F.FastGPLattice(F.Lattice(D, seed=3), lengthscales=ls, device="cuda")
+    else:
+        seq = F.DigitalNetB2(D, seed=3, generating_matrices=net_matrices(D, 3))
+        gp = F.FastGPDigitalNetB2(seq, alpha=1, lengthscales=ls, device="cuda")
+    gp.add_y_next(f_ackley(gp.get_x_next(2 ** M)))
+    xt = torch.rand((PV_N, D), generator=torch.Generator().manual_seed(5)).to("cuda")
+
+    def run(flag):
+        os.environ["FGP_WIDE_POST_VAR_QF"] = flag
+        return gp.post_var(xt)
+
+    res = {"family": family, "d": D, "n": 2 ** M, "N": PV_N, "ms": {"qf": [], "rows": [], "qf_again": []}, "peak_bytes": {}}
+    pv = {}
+    for key, flag in (("qf", "1"), ("rows", "0")):          # warm-up of both paths, and their peak allocation
+        run(flag)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        pv[key] = run(flag)
+        torch.cuda.synchronize()
+        res["peak_bytes"][key] = torch.cuda.max_memory_allocated() - base
+    res["max_abs_diff_over_kxx"] = float((pv["qf"] - pv["rows"]).abs().max() / gp._kdiag(xt).detach().abs().max())
+    for _ in range(5):
+        for key, flag in (("qf", "1"), ("rows", "0"), ("qf_again", "1")):
+            res["ms"][key].append(round(timed(lambda: run(flag), 1), 4))
+    med = {k: sorted(v)[len(v) // 2] for k, v in res["ms"].items()}
+    res["median_ms"] = med
+    res["aa_spread_ms"] = round(abs(med["qf"] - med["qf_again"]), 4)
+    res["speedup"] = round(med["rows"] / max(med["qf"], med["qf_again"]), 3)
+    print(json.dumps(res))
+
+
 def main():
-    global M, METRIC
+    global M, METRIC, D
     argv = list(sys.argv)
+    family = "lattice"
+    if "--d" in argv:
+        i = argv.index("--d")
+        D = int(argv[i + 1])
+        del argv[i:i + 2]
+    if "--family" in argv:
+        i = argv.index("--family")
+        family = argv[i + 1]
+        assert family in ("lattice", "net"), "--family lattice|net"
+        del argv[i:i + 2]
     if "--metric" in argv:
         i = argv.index("--metric")
         METRIC = argv[i + 1].upper()
@@ -108,6 +178,8 @@ def main():
     M = int(argv[2]) if len(argv) > 2 else M
     if mode in ("--fit", "--fit-trace"):
         return fit_mode(mode == "--fit-trace")
+    if mode == "--post-var":
+        return post_var_mode(family)
     gp = make()
     n = 2 ** M
     xt = torch.rand((NT, D), generator=torch.Generator().manual_seed(5)).to("cuda")
