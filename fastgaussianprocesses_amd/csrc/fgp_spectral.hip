@@ -1324,6 +1324,22 @@ __device__ __forceinline__ void wait_vmcnt(int n) {
 #ifndef FGP_SPEC_PF
 #define FGP_SPEC_PF 0     // (1: ~100 more VALU per wave, no measurable gain: profiles/r04ab2_basis_gen_prefetch.txt)
 #endif
+// k_spec_tile's chunk loop (A/B builds; the values and their order are the same in every form):
+//   FGP_SPEC_RD    the chunk's LDS reads: 0 plain loads (paired by the compiler into ds_read2st64_b64), 1 one
+//                  ds_read_b64 each at PPW < 4 (at PPW = 4 the form costs registers: d = 3 goes from 128 VGPRs,
+//                  the limit of its four waves per SIMD, to 130)
+//   FGP_SPEC_VMW   1: the counted vmcnt wait tests for 0 (every chunk but the first RING - 1) before the switch
+//   FGP_SPEC_ADDR  1: running DMA sources advanced by addition, 0: chunk-0 source + step * chunk per DMA
+#ifndef FGP_SPEC_RD
+#define FGP_SPEC_RD 1
+#endif
+#ifndef FGP_SPEC_VMW
+#define FGP_SPEC_VMW 1
+#endif
+#ifndef FGP_SPEC_ADDR
+#define FGP_SPEC_ADDR 1
+#endif
+typedef const volatile __attribute__((address_space(3))) double* LdsRead;
 
 // fgp_handoff_check (a test hook, fz.check): lane 0 of each storing wave reads back the partials it stored
 // (its own retired stores) and XORs their bits into the group's words [grp][g][q] with agent-scope atomics,
@@ -1422,8 +1438,14 @@ __global__ __launch_bounds__(kWG, 2) void k_spec_tile(Nll a, FitFuse fz) {
   // 64 in a Y row).
   constexpr int kMaxDma = kSpecMaxDma;              // tile <= 512 kMaxDma doubles: 1-KiB instructions, kMaxDma per wave
   static_assert(RING >= 2, "a chunk in flight under each chunk's compute");
+  // The chunks are issued in order, each once per iteration, so src0 runs: the next chunk's source, advanced by
+  // the step (an add per DMA; src0 + step * chunk was a 64-bit multiply per lane and DMA).
   const double* src0[kMaxDma];
+#if FGP_SPEC_ADDR
+  int step[kMaxDma];                                // (doubles: at most 64 (NS + G), a 32-bit register)
+#else
   int64_t step[kMaxDma];
+#endif
 #pragma unroll
   for (int t = 0; t < kMaxDma; ++t) {
     const int jj = w + 4 * t;
@@ -1432,13 +1454,18 @@ __global__ __launch_bounds__(kWG, 2) void k_spec_tile(Nll a, FitFuse fz) {
     const int64_t k = wg_base + sg * B;             // the segment's first frequency in chunk 0
     const int gy = min(goff + r - NS, G - 1);
     src0[t] = (r < NS ? a.basis + spec_at<NS>(k, r) : a.ysq + ysq_at(a, gy, k)) + 2 * col;
-    step[t] = r < NS ? NS * 64 : (a.ysq_chunked ? (int64_t)G * 64 : 64);
+    step[t] = r < NS ? NS * 64 : (a.ysq_chunked ? G * 64 : 64);
   }
   auto issue = [&](int c, double* buf) {
 #pragma unroll
     for (int t = 0; t < kMaxDma; ++t) {
       if (t < cnt_w) {
+#if FGP_SPEC_ADDR
+        const double* src = src0[t];
+        src0[t] = src + step[t];
+#else
         const double* src = src0[t] + step[t] * c;
+#endif
         __builtin_amdgcn_global_load_lds((glb_void*)src, (lds_void*)(buf + 128 * (w + 4 * t)), 16, 0, 0);
       }
     }
@@ -1562,7 +1589,13 @@ __global__ __launch_bounds__(kWG, 2) void k_spec_tile(Nll a, FitFuse fz) {
     }
 #endif
     // this wave's loads of chunk c have landed (chunks c + 1 .. issued - 1 may stay in flight)
+#if FGP_SPEC_VMW
+    // (nothing newer in flight at every chunk but the first RING - 1: that case first, the switch for the rest)
+    if (issued - 1 - c == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else wait_vmcnt(cnt_w * (issued - 1 - c));
+#else
     wait_vmcnt(cnt_w * (issued - 1 - c));
+#endif
     barrier_keep_vm();                              // ... every wave's; every wave done with chunk c - 1
     if (issued < nc && issued <= c + RING - 1) {    // into the slot of chunk c - 1
       issue(issued, lds + (issued % RING) * tile);
@@ -1570,15 +1603,35 @@ __global__ __launch_bounds__(kWG, 2) void k_spec_tile(Nll a, FitFuse fz) {
     }
     const double* buf = lds + (unsigned)(c % RING) * (unsigned)tile;
     if (active) {
-      const double* wb = buf + wofs;
       double phi[NS];
+      if constexpr (FGP_SPEC_RD == 1 && PPW < 4) {
+        // One ds_read_b64 per spectrum and Y: volatile reads are left alone, plain ones the compiler pairs into
+        // ds_read2st64_b64, which moves half the bytes per LDS cycle (MI355X_MICROARCH.md, LDS table).  (An empty
+        // slot, whose row may lie past the tile, re-reads the wave's first row.)
+        const LdsRead wb = (LdsRead)(buf + wofs), yb = (LdsRead)(buf + yofs);
+        double Y[PPW];
 #pragma unroll
-      for (int s = 0; s < NS; ++s) phi[s] = wb[64u * s];
-      const double* yb = buf + yofs;
+        for (int s = 0; s < NS; ++s) phi[s] = wb[64u * s];
 #pragma unroll
-      for (int p = 0; p < PPW; ++p)
-        if (on[p]) spec_terms<D>(phi, h[p], rootn, wl, yb[64u * p], acc[p]);
+        for (int p = 0; p < PPW; ++p) Y[p] = yb[on[p] ? 64u * p : 0u];
+#pragma unroll
+        for (int p = 0; p < PPW; ++p)
+          if (on[p]) spec_terms<D>(phi, h[p], rootn, wl, Y[p], acc[p]);
+      } else {
+        const double *wb = buf + wofs, *yb = buf + yofs;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) phi[s] = wb[64u * s];
+#pragma unroll
+        for (int p = 0; p < PPW; ++p)
+          if (on[p]) spec_terms<D>(phi, h[p], rootn, wl, yb[64u * p], acc[p]);
+      }
     }
+  }
+  if constexpr (PERSIST && FGP_SPEC_ADDR != 0) {
+    // the next iteration streams the same chunks: the running sources back to chunk 0
+#pragma unroll
+    for (int t = 0; t < kMaxDma; ++t)
+      if (t < cnt_w) src0[t] -= (int64_t)step[t] * nc;
   }
   {
   const TileArgs* ka = PERSIST ? tile_args<PERSIST>() : nullptr;

@@ -11,13 +11,20 @@
 //   DYN      blocks handed out by an atomic counter (per-block partials at the block's index: the same
 //            arithmetic whichever workgroup runs a block) vs a fixed block per workgroup
 //   SADDR    DMA source = wave-uniform base + lane offset (one VGPR) vs per-lane pointer arrays
-//   MODE     0 full, 1 stream only (no arithmetic), 2 arithmetic only (no loads)
+//   MODE     0 full, 1 stream only (no arithmetic), 2 arithmetic only (no loads), 3 (k_lab2) arithmetic on register
+//            values (no loads, no LDS reads)
+//   RD       (k_lab2) the chunk's LDS reads: 0 plain loads (the compiler pairs them into ds_read2st64_b64), 1 one
+//            ds_read_b64 each (volatile), 2 one ds_read_b64 each with counted lgkmcnt waits of our own: the lower
+//            half's polynomials of both problems under the upper half's and Y's reads; 3 that with the
+//            polynomials pinned above the waits (sched_barrier)
+//   ./tools/spec_lab r08        only the RD lines, each three times (the spread of repeated lines)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #define CK(x)                                                                \
@@ -273,6 +280,34 @@ __global__ __launch_bounds__(64 * G / PPW, WPC) void k_lab(Args a) {
 }
 
 
+typedef const volatile __attribute__((address_space(3))) double* LdsRead;
+template <int S, int E>
+__device__ __forceinline__ void lds_read_rows(unsigned addr, double* v) {
+  if constexpr (S < E) {
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(v[S]) : "v"(addr), "n"(512 * S) : "memory");
+    lds_read_rows<S + 1, E>(addr, v);
+  }
+}
+template <int N>
+__device__ __forceinline__ void lds_wait() { asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(N < 15 ? N : 15) : "memory"); }
+__device__ __forceinline__ void lds_landed(double& v) { asm volatile("" : "+v"(v)); }
+
+// terms() after the polynomial
+__device__ __forceinline__ void terms_tail(double P, const double* dp, const HypS& h, double rootn, double wl, double Y, Acc& acc) {
+  const double e = __builtin_fma(rootn, h.scale * P, h.noise);
+  const double r = rcp_nr(e);
+  acc.norm = __builtin_fma(Y, r, acc.norm);
+  int ex;
+  const double m = frexp(fabs(e), &ex);
+  acc.mant *= m;
+  acc.ex += ex;
+  const double g = r * __builtin_fma(-Y, r, wl);
+  acc.ge += g;
+  acc.gs = __builtin_fma(g, P, acc.gs);
+#pragma unroll
+  for (int j = 0; j < D; ++j) acc.gl[j] = __builtin_fma(g, dp[j], acc.gl[j]);
+}
+
 template <int N>
 __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
@@ -281,7 +316,7 @@ __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :
 //   AUX    cache-policy bits of the LDS-DMA loads (2 = nt)
 //   PROUS  a synthetic prologue of PROUS us before the loop (the fused kernel's deferred step: level-2 sums +
 //          Rprop), with PRE = 1 or 2 chunks issued in front of it
-template <int CK, int AUX, int PROUS, int PRE, int MODE>
+template <int CK, int AUX, int PROUS, int PRE, int MODE, int RD = 0>
 __global__ __launch_bounds__(256, 2) void k_lab2(Args a) {
   constexpr int W = 4, NI = 20 * CK, TPW = NI / W, T2 = TILE * CK, SPX = CK * NS * 64;
   static_assert(NI % W == 0, "whole DMA rounds");
@@ -310,7 +345,7 @@ __global__ __launch_bounds__(256, 2) void k_lab2(Args a) {
     }
   };
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if (MODE != 2) {
+  if (MODE < 2) {
     issue(0, lds);
     if (PRE == 2 && nc > 1) issue(1, lds + T2);
   }
@@ -320,19 +355,73 @@ __global__ __launch_bounds__(256, 2) void k_lab2(Args a) {
   }
   Acc acc[2];
   for (int c = 0; c < nc; ++c) {
-    if (PRE == 2 && c == 0 && nc > 1 && MODE != 2) wait_vm<TPW>();
+    if (PRE == 2 && c == 0 && nc > 1 && MODE < 2) wait_vm<TPW>();
     else wait_vm<0>();
     barrier_keep_vm();
-    if (MODE != 2 && c + 1 < nc && c + 1 >= PRE) issue(c + 1, lds + ((c + 1) & 1) * T2);
+    if (MODE < 2 && c + 1 < nc && c + 1 >= PRE) issue(c + 1, lds + ((c + 1) & 1) * T2);
     const double* buf = lds + (c & 1) * T2;
     if (MODE != 1) {
 #pragma unroll
       for (int sc = 0; sc < CK; ++sc) {
         double phi[NS];
+        if constexpr (MODE == 3) {
+          // no LDS reads in the loop: the chunk's values stay in registers, opaque to the compiler per chunk
+          double Y[2];
 #pragma unroll
-        for (int s = 0; s < NS; ++s) phi[s] = buf[(sc * NS + s) * 64 + lane];
+          for (int s = 0; s < NS; ++s) {
+            phi[s] = 1.0 / (1 + s + lane);
+            lds_landed(phi[s]);
+          }
 #pragma unroll
-        for (int p = 0; p < 2; ++p) terms(phi, h[p], rootn, wl, buf[SPX + (sc * G + 2 * w + p) * 64 + lane], acc[p]);
+          for (int p = 0; p < 2; ++p) {
+            Y[p] = 0.5 + p;
+            lds_landed(Y[p]);
+          }
+#pragma unroll
+          for (int p = 0; p < 2; ++p) terms(phi, h[p], rootn, wl, Y[p], acc[p]);
+        } else if constexpr (RD == 0) {
+#pragma unroll
+          for (int s = 0; s < NS; ++s) phi[s] = buf[(sc * NS + s) * 64 + lane];
+#pragma unroll
+          for (int p = 0; p < 2; ++p) terms(phi, h[p], rootn, wl, buf[SPX + (sc * G + 2 * w + p) * 64 + lane], acc[p]);
+        } else if constexpr (RD == 1) {
+          const LdsRead wb = (LdsRead)(buf + sc * NS * 64 + lane), yb = (LdsRead)(buf + SPX + (sc * G + 2 * w) * 64 + lane);
+          double Y[2];
+#pragma unroll
+          for (int s = 0; s < NS; ++s) phi[s] = wb[64 * s];
+#pragma unroll
+          for (int p = 0; p < 2; ++p) Y[p] = yb[64 * p];
+#pragma unroll
+          for (int p = 0; p < 2; ++p) terms(phi, h[p], rootn, wl, Y[p], acc[p]);
+        } else {
+          const LdsRead wb = (LdsRead)(buf + sc * NS * 64 + lane), yb = (LdsRead)(buf + SPX + (sc * G + 2 * w) * 64 + lane);
+          constexpr int H = NS / 2;
+          double Y[2], p0[2], p1[2], d0[2][D - 1], d1[2][D - 1];
+          lds_read_rows<0, NS>((unsigned)(uintptr_t)wb, phi);
+          lds_read_rows<0, 2>((unsigned)(uintptr_t)yb, Y);
+          lds_wait<H + 2>();
+#pragma unroll
+          for (int s = 0; s < H; ++s) lds_landed(phi[s]);
+#pragma unroll
+          for (int p = 0; p < 2; ++p) p0[p] = mlin<D - 1>(phi, h[p].ls, d0[p]);
+          if (RD == 3) __builtin_amdgcn_sched_barrier(0);
+          lds_wait<2>();
+#pragma unroll
+          for (int s = H; s < NS; ++s) lds_landed(phi[s]);
+#pragma unroll
+          for (int p = 0; p < 2; ++p) p1[p] = mlin<D - 1>(phi + H, h[p].ls, d1[p]);
+          if (RD == 3) __builtin_amdgcn_sched_barrier(0);
+          lds_wait<0>();
+#pragma unroll
+          for (int p = 0; p < 2; ++p) {
+            lds_landed(Y[p]);
+            double dp[D];
+#pragma unroll
+            for (int j = 0; j < D - 1; ++j) dp[j] = __builtin_fma(h[p].ls[D - 1], d1[p][j], d0[p][j]);
+            dp[D - 1] = p1[p];
+            terms_tail(__builtin_fma(h[p].ls[D - 1], p1[p], p0[p]), dp, h[p], rootn, wl, Y[p], acc[p]);
+          }
+        }
       }
     } else {
       acc[0].norm += buf[lane] + buf[SPX + 2 * w * 64 + lane];
@@ -537,6 +626,22 @@ int main(int argc, char** argv) {
            dur[grid * 9 / 10], endt[grid / 2], endt[grid * 9 / 10], xs, err);
     fflush(stdout);
   };
+  if (argc > 1 && !strcmp(argv[1], "r08")) {
+    // the LDS read forms of the chunk loop (k_lab2, the fused kernel's structure): full and arithmetic only
+    for (int rep = 0; rep < 3; ++rep) {
+      run("lab2 ck1", k_lab2<1, 0, 0, 1, 0>, 2, 512, 16, true, 256, 1);
+      run("lab2 ck1 compute", k_lab2<1, 0, 0, 1, 2>, 2, 512, 16, false, 256, 1);
+      run("lab2 ck1 rd1", k_lab2<1, 0, 0, 1, 0, 1>, 2, 512, 16, true, 256, 1);
+      run("lab2 ck1 rd1 compute", k_lab2<1, 0, 0, 1, 2, 1>, 2, 512, 16, false, 256, 1);
+      run("lab2 ck1 rd2", k_lab2<1, 0, 0, 1, 0, 2>, 2, 512, 16, true, 256, 1);
+      run("lab2 ck1 rd2 compute", k_lab2<1, 0, 0, 1, 2, 2>, 2, 512, 16, false, 256, 1);
+      run("lab2 ck1 rd3", k_lab2<1, 0, 0, 1, 0, 3>, 2, 512, 16, true, 256, 1);
+      run("lab2 ck1 rd3 compute", k_lab2<1, 0, 0, 1, 2, 3>, 2, 512, 16, false, 256, 1);
+      run("lab2 ck1 valu only", k_lab2<1, 0, 0, 1, 3>, 2, 512, 16, false, 256, 1);
+      run("lab2 ck1 valu only 1 chunk", k_lab2<1, 0, 0, 1, 3>, 2, 512, 1, false, 256, 1);
+    }
+    return 0;
+  }
   const bool all = argc > 1;   // the slower families measured in r04a / r04b (profiles/r04_lab.jsonl)
   // the current structure: fixed block per workgroup, 512 x 16 chunks, pointer arrays, 2-slot ring
   run("fixed ptr r2", k_lab<2, false, false, 0, 2>, 2, 512, 16, true);
