@@ -94,13 +94,16 @@ __global__ __launch_bounds__(kWG) void k_post_mean(const double* __restrict__ xt
   // Folded B4 factors (ORD = 4, every a != 0): 1 + a B4(t) = a (u^2 + c'), c' = (1 - a/30) / a, with
   // prod_j a_j moved into the output scale -- 4 operations per dimension and pair instead of 5 (this
   // kernel is FP64-VALU bound).  a c' = 1 - a/30 = O(1), so the rounding stays at the factor's ulp.
+  // Taken only while every |a| is in [2^-120, 2^120]: prod_j a_j and prod_j c'_j then stay normal for D <= 8 (a
+  // lengthscale of 1e-60 at D = 6 underflows the one and overflows the other: 0 * inf); outside, and at a == 0, the
+  // unfolded factors below.  Decided once per thread from the launch constants.
   bool fold = FAM == 0 && ORD == 4;
   double cp[NB][D];
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
 #pragma unroll
     for (int j = 0; j < D; ++j) {
-      fold = fold && fa[b][j] != 0.0;
+      fold = fold && fabs(fa[b][j]) >= 0x1p-120 && fabs(fa[b][j]) <= 0x1p120;
       cp[b][j] = fc[b][j] / fa[b][j];
     }
   }
@@ -805,12 +808,15 @@ extern "C" {
 int fgp_post_mean(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int tbits, const int* order,
                   const double* coef, const double* hyp, int Gk, const double* coeffs, int64_t coeff_stride, int B,
                   double* out, int64_t out_stride, double* work, int64_t chunk, void* stream) {
-  if (B > kPmB && Gk == B && N > 0) {
+  if (B > kPmB && Gk == B) {
     // every output with its own hyper-parameters (per-output batches, e.g. C5 per-output: 512 outputs): the
     // blocks of kPmB outputs as the problems of ONE launch (blockIdx.z; the arithmetic of one block per launch),
     // the B mod kPmB remaining outputs in a second
-    if (N < 0 || n < 1 || d < 1 || d > FGP_MAX_D || chunk < 1 || !xt || !z || !hyp || !coeffs || !out || !work)
-      return set_error(kErrInvalid, "fgp_post_mean: bad sizes / null pointer");
+    if (N < 0 || n < 1 || d < 1 || d > FGP_MAX_D || chunk < 1)
+      return set_error(kErrInvalid, "fgp_post_mean: bad sizes (N=%lld n=%lld d=%d B=%d Gk=%d)", (long long)N,
+                       (long long)n, d, B, Gk);
+    if (N == 0) return kOk;
+    if (!xt || !z || !hyp || !coeffs || !out || !work) return set_error(kErrInvalid, "fgp_post_mean: null pointer");
     if (out_stride != N) return set_error(kErrInvalid, "fgp_post_mean: B > %d needs out_stride == N", kPmB);
     PredSpec spec;
     int rc = make_spec(family, d, order, coef, spec);
