@@ -1,4 +1,5 @@
-"""Extended-precision reference of the d <= 8 prediction kernels (csrc/fgp_predict.hip), with first-order bounds.
+"""Extended-precision reference of the prediction kernels (csrc/fgp_predict.hip, d <= 8; generic in d, so also of the
+wide ones, 9 <= d <= 64: csrc/fgp_wide.hip and k_wide_qf_rows) and of the wide first column, with first-order bounds.
 
 The same arithmetic setup as tests/spectral_reference.py (np.longdouble where its eps is below 2e-19, mpmath at 40
 digits otherwise; its _x / _xs widen fp64 inputs exactly).  Every function takes the very fp64 / int64 arrays handed to
@@ -45,6 +46,11 @@ quadform      q = sum_k wa_k |ft(r)_k|^2, ft the orthonormal transform of includ
     the 2 |r~_0|.  ||B_r||_2 is the rows' own bound.
 
 post_var      max(0, K(x, x) - q), K(x, x) = scale prod_j (1 + l_j part0_j);  B = B_q + K(x, x).
+
+lattice_parts, net_parts   the parts arrays [d, n] of the first column (fgp_wide_lattice_parts / fgp_wide_net_parts),
+              bounds as for a factor's part above.
+k1, k1_bwd    k1[g, i] = s_g prod_j (1 + l_gj p_ji) (fgp_wide_k1) and its adjoint for the natural scale and lengthscale
+              rows (fgp_wide_k1_bwd), bf_j = 1 + |l_j p_j|; see the functions.
 """
 from fractions import Fraction
 
@@ -117,18 +123,26 @@ def bernoulli_split(order, t):
 
 def _product(scale, f, b):
     """K = scale prod_j f_j and B_K = |scale| sum_j b_j prod_{i != j} |f_i| (f, b: lists over j)."""
-    d = len(f)
     K = f[0] * 0 + scale
-    for j in range(d):
-        K = K * f[j]
+    for fj in f:
+        K = K * fj
     BK = f[0] * 0
-    for j in range(d):
-        t = b[j]
-        for i in range(d):
-            if i != j:
-                t = t * abs(f[i])
-        BK = BK + t
+    for bj, lo in zip(b, _leave_one_out([abs(fj) for fj in f])):
+        BK = BK + bj * lo
     return K, abs(scale) * BK
+
+
+def _leave_one_out(f):
+    """[prod_{i != j} f_i for j]: prefix times suffix products, never a quotient (a factor may be zero)."""
+    d = len(f)
+    suf = [f[0] * 0 + 1] * (d + 1)
+    for j in range(d - 1, -1, -1):
+        suf[j] = suf[j + 1] * f[j]
+    out, pre = [], f[0] * 0 + 1
+    for j in range(d):
+        out.append(pre * suf[j + 1])
+        pre = pre * f[j]
+    return out
 
 
 def net_bits(x, tbits):
@@ -299,3 +313,99 @@ def post_var(k0, q, Bq):
     """(max(0, K(x, x) - q), B_q + K(x, x)); k0 broadcasts against q."""
     v = k0 - q
     return v * np.where(v > 0, 1, 0), Bq + abs(k0)
+
+
+# ------------------------------------------------------------------------------------------------ first column
+def lattice_parts(x, z, orders, coef):
+    """(parts, B) [d, n]: coef_j B_order_j((x[i, j] - z[j]) mod 1) of fp64 x [n, d] (any row stride) and z [d].  B:
+    |coef| (|B_n(t) - B_n(0)| + |B_n(0)|), the split at the constant term, plus the effect on the part of the kernel's
+    rounded distance, |coef B_n'(t)| (|x - z| + [x < z]): the subtraction rounds at |x - z|, and the shift of a
+    negative remainder into [0, 1) rounds once more, below 1."""
+    x = np.asarray(x, dtype=np.float64)
+    n, d = x.shape
+    P, B = [], []
+    for j in range(d):
+        diff = _x(x[:, j]) - _xs(np.float64(z[j]))
+        dl = diff - _floor(diff)
+        top, b0, der = bernoulli_split(orders[j], dl)
+        c = _xs(np.float64(coef[j]))
+        P.append(c * (top + b0))
+        B.append(abs(c) * (abs(top) + abs(b0)) + abs(c * der) * (abs(diff) + np.where(x[:, j] < z[j], 1, 0)))
+    return np.stack(P), np.stack(B)
+
+
+def net_parts(xb, z, orders, t):
+    """(parts, B) [d, n] of int64 xb [n, d] and z [d], delta = xb XOR z: order 1 the closed form
+    1 - 3 2^(floor(log2 delta) - t) (1 at delta = 0) with B = 1 + 3 2^(..), orders 2..4 walsh_omega with B = W_a."""
+    xb = np.asarray(xb)
+    n, d = xb.shape
+    P, B = [], []
+    for j in range(d):
+        delta = xb[:, j].astype(np.uint64) ^ np.uint64(int(z[j]))
+        if int(orders[j]) <= 1:
+            w = np.where(delta != 0, 1, 0) * (3 * _pow2(floor_log2(delta) - int(t)))
+            P.append(1 - w)
+            B.append(1 + w)
+        else:
+            om = walsh_omega(int(orders[j]), delta, int(t))
+            P.append(om)
+            B.append(om * 0 + _q(WALSH_W[int(orders[j])]))
+    return np.stack(P), np.stack(B)
+
+
+def _k1_factors(parts, ls, g):
+    l = _x(np.asarray(ls, dtype=np.float64))[g]
+    p = _x(np.asarray(parts, dtype=np.float64))
+    d = p.shape[0]
+    return p, [1 + l[j] * p[j] for j in range(d)], [1 + abs(l[j] * p[j]) for j in range(d)]
+
+
+def k1(parts, scale, ls):
+    """(k1, B) [G, n]: scale_g prod_j f_gji, f = 1 + l_gj parts[j, i], of fp64 parts [d, n], scale [G], ls [G, d];
+    B through _product with bf_j = 1 + |l_j p_j|."""
+    s = _x(np.asarray(scale, dtype=np.float64))
+    K, B = [], []
+    for g in range(s.shape[0]):
+        _, f, bf = _k1_factors(parts, ls, g)
+        k, b = _product(s[g], f, bf)
+        K.append(k)
+        B.append(b)
+    return np.stack(K), np.stack(B)
+
+
+def k1_bwd(parts, scale, ls, u):
+    """(dscale [G], B [G], dls [G, d], B [G, d]) of u [G, n]:
+        dscale_g = sum_i u_gi prod_j f_gji,   dls_gj = sum_i u_gi s_g p_ji prod_{j' != j} f_gj'i,
+    the leave-one-out product formed as a product.  Bound of a term: that of the product of its factors (_product
+    over them), times |u| (and |s p|), summed over i."""
+    s = _x(np.asarray(scale, dtype=np.float64))
+    uu = _x(np.asarray(u, dtype=np.float64))
+    ds, Bs, dl, Bl = [], [], [], []
+    for g in range(s.shape[0]):
+        p, f, bf = _k1_factors(parts, ls, g)
+        d = len(f)
+        af = [abs(v) for v in f]
+        k, b = _product(XT(1), f, bf)
+        ds.append((uu[g] * k).sum())
+        Bs.append((abs(uu[g]) * b).sum())
+        # leave-one-out values, and the bounds sum_{i != j} bf_i prod_{k != i, j} |f_k| from prefix / suffix pairs:
+        # (pv, pb) = (prod |f|, sum_i bf_i prod_{k != i} |f_k|) of the factors before j, (sv, sb) of those after
+        one, zero = f[0] * 0 + 1, f[0] * 0
+        sv, sb = [one] * (d + 1), [zero] * (d + 1)
+        sval = [one] * (d + 1)
+        for j in range(d - 1, -1, -1):
+            sval[j] = sval[j + 1] * f[j]
+            sb[j] = sb[j + 1] * af[j] + bf[j] * sv[j + 1]
+            sv[j] = sv[j + 1] * af[j]
+        pval, pv, pb = one, one, zero
+        row, brow = [], []
+        for j in range(d):
+            w = uu[g] * s[g] * p[j]
+            row.append((w * (pval * sval[j + 1])).sum())
+            brow.append((abs(w) * (pb * sv[j + 1] + pv * sb[j + 1])).sum())
+            pval = pval * f[j]
+            pb = pb * af[j] + bf[j] * pv
+            pv = pv * af[j]
+        dl.append(np.stack(row))
+        Bl.append(np.stack(brow))
+    return np.stack(ds), np.stack(Bs), np.stack(dl), np.stack(Bl)
