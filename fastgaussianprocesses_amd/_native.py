@@ -16,6 +16,7 @@ ABI_VERSION = 20
 MT_MAX_TASKS = 16
 MAX_D = 8
 WIDE_MAX_D = 64                # the fgp_wide_* entry points: MAX_D < d <= WIDE_MAX_D
+WIDE_MT_MAX_P = 16             # derivative multi-index pairs of the fused fgp_wide_mt_* entry points
 PARTS_ARRAY = 0
 PARTS_LATTICE = 1
 
@@ -211,6 +212,15 @@ _SIGNATURES = {
     # addition to ABI 20: the posterior variance's quadratic form for wide d
     "fgp_wide_post_var_qf": [_c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd, _c_vp,
                              _c_i64, _c_vp, _c_i64, _c_int, _c_vp, _c_vp, _c_vp, _c_vp],
+    # addition to ABI 20: the multitask / derivative-informed task-pair kernel for wide d (host spec tables)
+    "fgp_wide_mt_parts": [_c_int, _c_vp, _c_i64, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd,
+                          _c_pd, _c_int, _c_vp, _c_vp],
+    "fgp_wide_mt_k1": [_c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_vp, _c_vp, _c_int, _c_vp, _c_vp],
+    "fgp_wide_mt_k1_bwd_work": [_c_i64, _c_int, _c_int, _c_int, _c_pl],
+    "fgp_wide_mt_k1_bwd": [_c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_vp, _c_vp, _c_int, _c_vp, _c_vp, _c_vp, _c_vp,
+                           _c_vp],
+    "fgp_wide_mt_rows": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd, _c_pd, _c_pi, _c_pd,
+                         _c_int, _c_vp, _c_int, _c_vp, _c_vp],
 }
 
 

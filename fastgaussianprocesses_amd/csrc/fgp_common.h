@@ -745,6 +745,32 @@ __device__ __forceinline__ double bernoulli(int order, double x) {
   }
 }
 
+// Bernoulli polynomial of any order 1..8: even orders by the u = x (x - 1) form shared with the fit
+// kernels (bernoulli()), odd orders B_{2k+1} by Horner's rule in x as qmcpy.kernel_methods.bernoulli_poly.
+__device__ __forceinline__ double bernoulli_any(int order, double x) {
+  switch (order) {
+    case 1: return x - 0.5;
+    case 3: return __builtin_fma(__builtin_fma(x, x, -1.5 * x), x, 0.5 * x);
+    case 5: {
+      double y = x - 2.5;
+      y = __builtin_fma(y, x, 5.0 / 3.0);
+      y = y * x;
+      y = __builtin_fma(y, x, -1.0 / 6.0);
+      return y * x;
+    }
+    case 7: {
+      double y = x - 3.5;
+      y = __builtin_fma(y, x, 3.5);
+      y = y * x;
+      y = __builtin_fma(y, x, -7.0 / 6.0);
+      y = y * x;
+      y = __builtin_fma(y, x, 1.0 / 6.0);
+      return y * x;
+    }
+    default: return bernoulli(order, x);
+  }
+}
+
 // Order-1 Walsh part for an XOR distance (fast_gp_digital_net_b2.py:297-298).
 __device__ __forceinline__ double walsh1(unsigned long long delta, int t) {
   if (delta == 0ull) return 6.0 * (1.0 / 6.0 - 0.0);

@@ -29,32 +29,7 @@ namespace fgp {
 
 // ------------------------------------------------------------------------------------------------
 // derivative kernel parts
-// Bernoulli polynomial of any order 1..8: even orders by the u = x (x - 1) form shared with the fit
-// kernels (bernoulli()), odd orders B_{2k+1} by Horner's rule in x as qmcpy.kernel_methods.bernoulli_poly.
-__device__ __forceinline__ double bernoulli_any(int order, double x) {
-  switch (order) {
-    case 1: return x - 0.5;
-    case 3: return __builtin_fma(__builtin_fma(x, x, -1.5 * x), x, 0.5 * x);
-    case 5: {
-      double y = x - 2.5;
-      y = __builtin_fma(y, x, 5.0 / 3.0);
-      y = y * x;
-      y = __builtin_fma(y, x, -1.0 / 6.0);
-      return y * x;
-    }
-    case 7: {
-      double y = x - 3.5;
-      y = __builtin_fma(y, x, 3.5);
-      y = y * x;
-      y = __builtin_fma(y, x, -7.0 / 6.0);
-      y = y * x;
-      y = __builtin_fma(y, x, 1.0 / 6.0);
-      return y * x;
-    }
-    default: return bernoulli(order, x);
-  }
-}
-
+// (bernoulli_any: fgp_common.h)
 // parts[i][k][p][j] for x_i (i < N) against z_k (k < M), P (beta, kappa) pairs, d dimensions
 // (zip: N == M, the pairs (x_i, z_i) only, parts[i][p][j]):
 //   lattice: coef[p][j] * B_{order[p][j]}((x_ij - z_kj) mod 1)

@@ -1545,10 +1545,34 @@ class AbstractFastGP(torch.nn.Module):
     def _parts_pairs(self, x, z, beta0, beta1, zip_pairs=False, check=True):
         """_kernel_parts (abstract_fast_gp.py:173-180) for all (x_i, z_k) pairs -> [N, M, p0, p1, d]
         (or the (x_i, z_i) pairs -> [N, p0, p1, d])."""
+        if ops._wide(self.d):
+            # d > 8: the dimension-major parts of fgp_wide_mt_parts [P, d, E] through a permuted view
+            xa, za = self._kargs(x, check), self._kargs(z, check)
+            p = ops.wide_mt_parts(self._wide_mt_spec(beta0, beta1), xa, za, zip_pairs).permute(2, 0, 1)
+            lead = (xa.shape[0],) if zip_pairs else (xa.shape[0], za.shape[0])
+            return p.reshape(lead + (len(beta0), len(beta1), self.d))
         order, coef, add = self._pair_spec(beta0, beta1)
         p = ops.mt_parts(self._FAMILY, self._kargs(x, check), self._kargs(z, check), order, coef, add, self._tbits(),
                          zip_pairs)
         return p.reshape(p.shape[:-2] + (len(beta0), len(beta1), self.d))
+
+    def _wide_mt_spec(self, beta0, beta1, c0=None, c1=None):
+        """ops.WideMtSpec of the pair (beta0, c0), (beta1, c1): _pair_spec's tables, ind = (beta0 + beta1 == 0) and
+        cc[p] = c0[p0] c1[p1] (ones when no coefficients are given: the parts do not use them); memoised."""
+        b0, b1 = beta0.detach().cpu().to(torch.int64), beta1.detach().cpu().to(torch.int64)
+        if c0 is None:
+            cc = [1.0] * (len(b0) * len(b1))
+        else:
+            h0, h1 = c0.detach().cpu().to(torch.float64), c1.detach().cpu().to(torch.float64)
+            cc = (h0[:, None] * h1[None, :]).reshape(-1).tolist()
+        key = (tuple(b0.shape), tuple(b0.reshape(-1).tolist()), tuple(b1.shape), tuple(b1.reshape(-1).tolist()), tuple(cc),
+               tuple(self._alphas))
+        memo = self.__dict__.setdefault("_wide_mt_spec_memo", {})
+        if key not in memo:
+            order, coef, add = self._pair_spec(b0, b1)
+            ind = ((b0[:, None, :] + b1[None, :, :]) == 0).to(torch.int64).reshape(-1, self.d).tolist()
+            memo[key] = ops.WideMtSpec(self._FAMILY, order, coef, add, ind, cc, self._tbits())
+        return memo[key]
 
     def _kernel_from_parts(self, parts, beta0, beta1, c0, c1):
         """abstract_fast_gp.py:181-191."""

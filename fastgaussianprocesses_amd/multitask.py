@@ -8,6 +8,8 @@ predictions; abstract_fast_gp.py:29-31,155-191 task-pair caches and derivative k
 
 Where the work runs:
   * derivative kernel parts, per task pair and for prediction rows  -> fgp_mt_parts (HIP)
+  * at 9 <= d <= 64: dimension-major parts, the fused first column of a task pair and its
+    adjoint, kernel rows from the points                              -> fgp_wide_mt_parts / _k1 / _k1_bwd / _rows
   * ft / ift of every task's data and first-column kernels           -> fgp_fftbr / fgp_ifftbr / fgp_fwht
   * the T x T block-eigenvalue inverse (util.py:275-337), its solves,
     logdet and the MLL gradient                                      -> fgp_mt_factor / fgp_mt_solve /
@@ -531,12 +533,21 @@ class MultiTaskFastGP(AbstractFastGP):
 
     # ------------------------------------------------------------------ kernel parts and kernels
     # (_pair_spec, _kargs, _parts_pairs, _kernel_from_parts: AbstractFastGP, fast_gp.py)
-    def _kmat_block(self, x, z, ta, tb, zip_pairs=False, chunk_elems=1 << 24):
-        """K_{ta,tb}(x_i, z_k) -> [*param batch, N, M] ([*, N] with zip_pairs), chunked over x."""
+    def _kmat_block(self, x, z, ta, tb, zip_pairs=False, chunk_elems=1 << 24, z_dn=None):
+        """K_{ta,tb}(x_i, z_k) -> [*param batch, N, M] ([*, N] with zip_pairs), chunked over x.  z_dn: z as the wide
+        rows kernel takes it (dimension-major [d, M], _xb_dm), when the caller has it cached."""
         b0, b1 = self._derivs_h[ta], self._derivs_h[tb]
         c0, c1 = self.derivatives_coeffs[ta], self.derivatives_coeffs[tb]
         bd0, bd1 = self.derivatives[ta], self.derivatives[tb]
         N = x.shape[0]
+        spec = self._wide_pair_spec(ta, tb)
+        if spec is not None and not self._gradmode() and N > 0 and z.shape[0] > 0 and torch.is_floating_point(x):
+            # d > 8 without an autograd graph: the kernel rows from the points (fgp_wide_mt_rows), no parts array
+            xc = x.to(device=self.device, dtype=torch.float64)
+            assert bool(((0 <= xc) & (xc <= 1)).all()), "x should have all elements in [0,1]"
+            rows = ops.wide_mt_rows(spec, xc, z_dn if z_dn is not None else self._kargs(z).T.contiguous(),
+                                    self._wide_hyp_rows(), zip_pairs)
+            return rows.reshape(self._wide_param_rows() + rows.shape[1:])
         per = max(1, (1 if zip_pairs else z.shape[0]) * len(b0) * len(b1) * self.d)
         step = max(1, chunk_elems // per)
         outs = []
@@ -551,12 +562,67 @@ class MultiTaskFastGP(AbstractFastGP):
                                            bd0, bd1, c0, c1)
         return torch.cat(outs, -1 if zip_pairs else -2)
 
+    # ------------------------------------------------------------------ wide inputs (d > 8)
+    def _wide_pair_spec(self, ta, tb):
+        """ops.WideMtSpec of the task pair when its kernel takes the fused wide entry points (d > 8, at most 16
+        derivative multi-index pairs, FGP_WIDE_FUSED not 0), else None: the torch formulation over the parts."""
+        if not ops._wide(self.d) or not ops.wide_fused():
+            return None
+        memo = self.__dict__.setdefault("_wide_pair_specs", {})
+        if (ta, tb) not in memo:
+            memo[ta, tb] = self._wide_mt_spec(self._derivs_h[ta], self._derivs_h[tb], self.derivatives_coeffs[ta],
+                                              self.derivatives_coeffs[tb])
+        spec = memo[ta, tb]
+        return spec if spec.fused else None
+
+    def _wide_param_rows(self):
+        """The hyper-parameter rows of the kernel: the broadcast batch shape of scale and lengthscales."""
+        return tuple(torch.broadcast_shapes(self.scale.shape[:-1], self.lengthscales.shape[:-1]))
+
+    def _wide_hyp_rows(self):
+        """[G, 1 + d] (scale, lengthscales) over _wide_param_rows, for fgp_wide_mt_rows."""
+        rows = self._wide_param_rows()
+        s, ls = self.scale.detach(), self.lengthscales.detach()
+        return torch.cat([s.expand(rows + (1,)).reshape(-1, 1), ls.expand(rows + (self.d,)).reshape(-1, self.d)], -1)
+
+    def _wide_k1(self, spec, parts_dm):
+        """First-column kernel [*param rows, n] from dimension-major parts [P, d, n] (fgp_wide_mt_k1, and its adjoint
+        under autograd)."""
+        rows = self._wide_param_rows()
+        k1 = ops.wide_mt_k1(spec, parts_dm, self.scale.expand(rows + (1,)).reshape(-1),
+                            self.lengthscales.expand(rows + (self.d,)).reshape(-1, self.d))
+        return k1.reshape(rows + (parts_dm.shape[-1],))
+
+    def _k1parts_dm(self, task0, task1, n, n0=0):
+        """The derivative parts of task0's points n0 .. n - 1 against task1's first point, dimension-major [P, d,
+        n - n0] (fgp_wide_mt_parts; d > 8); the whole prefix (n0 = 0) is cached like get_k1parts."""
+        key = ("dm", task0, task1, n)
+        if n0 == 0 and key in self._parts_cache:
+            return self._parts_cache[key]
+        spec = self._wide_mt_spec(self._derivs_h[task0], self._derivs_h[task1])
+        parts = ops.wide_mt_parts(spec, self.get_xb(task0, n)[n0:], self.get_xb(task1, 1))
+        if n0 == 0:
+            self._parts_cache[key] = parts
+        return parts
+
+    def _xb_dm(self, task, n):
+        """Task's first n points dimension-major [d, n] (float64 lattice / int64 net), as fgp_wide_mt_rows takes the
+        training points; cached per (task, n)."""
+        memo = self.__dict__.setdefault("_xb_dm_cache", {})
+        if (task, n) not in memo:
+            memo[task, n] = self.get_xb(task, n).T.contiguous()
+        return memo[task, n]
+
     def get_k1parts(self, task0, task1, n=None):
         """_K1PartsSeq[task0, task1][:n] (util.py:50-62): points of task0 vs the first point of task1."""
         assert 0 <= task0 < self.num_tasks and 0 <= task1 < self.num_tasks
         n = self._ns[task0] if n is None else int(n)
         assert n >= 0
         key = (task0, task1, n)
+        if ops._wide(self.d):
+            # d > 8: a view of the dimension-major array [P, d, n]
+            p = self._k1parts_dm(task0, task1, n).permute(2, 0, 1)
+            return p.reshape((n, len(self._derivs_h[task0]), len(self._derivs_h[task1]), self.d))
         if key not in self._parts_cache:
             xa = self.get_xb(task0, n)
             zb = self.get_xb(task1, 1)
@@ -575,9 +641,17 @@ class MultiTaskFastGP(AbstractFastGP):
             return self._kernel_from_parts(parts, self.derivatives[task0], self.derivatives[task1],
                                            self.derivatives_coeffs[task0], self.derivatives_coeffs[task1])
 
+        spec = self._wide_pair_spec(task0, task1)
+
         def f():
             half = self._cache.get(("lam", (task0, task1, n // 2), True, False)) \
                 if (n >= 4 and not self._gradmode()) else None
+            if spec is not None:
+                # d > 8: the fused first column from the dimension-major parts (the new half only when doubling)
+                if half is not None:
+                    return ops.double_update(self._FAMILY, half,
+                                             self.ft(self._wide_k1(spec, self._k1parts_dm(task0, task1, n, n // 2))))
+                return self.ft(self._wide_k1(spec, self._k1parts_dm(task0, task1, n)))
             if half is not None:
                 # _LamCaches doubling (util.py:113-132): one DIT stage from the cached lam at n/2 and ft
                 # of the first-column kernel over the new half of task0's points
@@ -815,7 +889,8 @@ class MultiTaskFastGP(AbstractFastGP):
         for t in tasks:
             blocks = []
             for l in range(self.num_tasks):
-                kb = self._kmat_block(x, self.get_xb(l, ns[l]), t, l)
+                z_dn = self._xb_dm(l, ns[l]) if self._wide_pair_spec(t, l) is not None and ns[l] > 0 else None
+                kb = self._kmat_block(x, self.get_xb(l, ns[l]), t, l, z_dn=z_dn)
                 blocks.append(Kt[..., t, l, None, None] * kb)
             bshape = torch.broadcast_shapes(*[b.shape[:-2] for b in blocks])
             rows.append(torch.cat([b.expand(bshape + b.shape[-2:]) for b in blocks], -1)[..., None, :, :])

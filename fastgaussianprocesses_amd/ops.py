@@ -716,6 +716,148 @@ def mt_parts(family, x, z, order, coef, add, tbits=0, zip_pairs=False):
     return out
 
 
+# ------------------------------------------------------------------------------------- wide multitask kernel
+class WideMtSpec(object):
+    """The spec of one task pair's kernel at d > 8 (abstract_fast_gp.py:173-191) as the fgp_wide_mt_* entry points
+    take it: host tables order / coef / add / ind [P, d] and the weights cc [P] (p = p0-major), made once per pair."""
+
+    def __init__(self, family, order, coef, add, ind, cc, tbits=0):
+        self.family, self.tbits = int(family), int(tbits)
+        self.P, self.d = len(order), len(order[0])
+        assert all(len(t) == self.P and all(len(r) == self.d for r in t) for t in (order, coef, add, ind))
+        assert len(cc) == self.P
+        self.tables = (order, coef, add, ind, cc)
+        flat = lambda t: [v for r in t for v in r]
+        self.order, self.coef, self.add = N.int_array(flat(order)), N.double_array(flat(coef)), N.double_array(flat(add))
+        self.ind, self.cc = N.int_array(flat(ind)), N.double_array(cc)
+        self._blocks = {}
+
+    @property
+    def fused(self):
+        """P within the fused entry points' limit (more pairs: the torch formulation over the parts)."""
+        return self.P <= N.WIDE_MT_MAX_P
+
+    def block(self, p0, p1):
+        """The pairs p0 .. p1 - 1 as a spec of their own (the parts of different pairs are independent)."""
+        if (p0, p1) == (0, self.P):
+            return self
+        if (p0, p1) not in self._blocks:
+            self._blocks[p0, p1] = WideMtSpec(self.family, *[t[p0:p1] for t in self.tables], tbits=self.tbits)
+        return self._blocks[p0, p1]
+
+
+def _mt_points(family, x):
+    x = x.to(torch.float64 if family == LATTICE else torch.int64)
+    return x if x.stride(-1) == 1 else x.contiguous()
+
+
+def wide_mt_parts(spec, x, z, zip_pairs=False):
+    """Derivative kernel parts at d > 8 (fgp_wide_mt_parts), dimension-major: x [N, d], z [M, d] (float64 lattice /
+    int64 net points) -> [P, d, N M] (e = i M + k), or [P, d, N] with zip_pairs (N == M).  Any P: the entry point takes
+    16 pairs a call."""
+    require_device(x, "wide_mt_parts")
+    x, z = _mt_points(spec.family, x), _mt_points(spec.family, z)
+    Nx, d = x.shape
+    M = z.shape[0]
+    assert d == spec.d and z.shape[1] == d and (not zip_pairs or Nx == M)
+    E = Nx if zip_pairs else Nx * M
+    out = torch.empty((spec.P, d, E), dtype=torch.float64, device=x.device)
+    for p0 in range(0, spec.P, N.WIDE_MT_MAX_P):
+        p1 = min(spec.P, p0 + N.WIDE_MT_MAX_P)
+        b = spec.block(p0, p1)
+        N.call("fgp_wide_mt_parts", b.family, N.ptr(x), x.stride(0) if Nx > 1 else d, Nx, N.ptr(z),
+               z.stride(0) if M > 1 else d, M, int(bool(zip_pairs)), d, b.P, b.order, b.coef, b.add, b.tbits,
+               N.ptr(out[p0:p1]), _stream(x))
+    return out
+
+
+def _mt_rows_args(scale_rows, ls_rows, d):
+    G = scale_rows.numel()
+    assert ls_rows.shape == (G, d)
+    return (G, scale_rows.detach().to(torch.float64).reshape(G).contiguous(),
+            ls_rows.detach().to(torch.float64).contiguous())
+
+
+def wide_mt_k1_raw(spec, parts, scale_rows, ls_rows):
+    """k1[g, i] = scale_rows[g] sum_p cc[p] prod_j (ind[p, j] + ls_rows[g, j] parts[p, j, i]) -> [G, n]
+    (fgp_wide_mt_k1); parts [P, d, n]."""
+    require_device(parts, "wide_mt_k1")
+    P, d, n = parts.shape
+    assert parts.dtype == torch.float64 and parts.is_contiguous() and (P, d) == (spec.P, spec.d)
+    G, sc, ls = _mt_rows_args(scale_rows, ls_rows, d)
+    k1 = torch.empty((G, n), dtype=torch.float64, device=parts.device)
+    N.call("fgp_wide_mt_k1", N.ptr(parts), n, d, P, spec.ind, spec.cc, N.ptr(sc), N.ptr(ls), G, N.ptr(k1), _stream(parts))
+    return k1
+
+
+def wide_mt_k1_bwd_raw(spec, parts, scale_rows, ls_rows, u):
+    """(dL/dscale_rows [G], dL/dls_rows [G, d]) from u = dL/dk1 [G, n] (fgp_wide_mt_k1_bwd)."""
+    P, d, n = parts.shape
+    G, sc, ls = _mt_rows_args(scale_rows, ls_rows, d)
+    u = resolved(u.to(torch.float64)).reshape(G, n).contiguous()
+    ds = torch.empty((G,), dtype=torch.float64, device=parts.device)
+    dl = torch.empty((G, d), dtype=torch.float64, device=parts.device)
+    wlen = ctypes.c_int64(0)
+    N.call("fgp_wide_mt_k1_bwd_work", n, d, P, G, ctypes.byref(wlen))
+    work = torch.empty((wlen.value,), dtype=torch.float64, device=parts.device)
+    N.call("fgp_wide_mt_k1_bwd", N.ptr(parts), n, d, P, spec.ind, spec.cc, N.ptr(sc), N.ptr(ls), G, N.ptr(u), N.ptr(ds),
+           N.ptr(dl), N.ptr(work), _stream(parts))
+    return ds, dl
+
+
+class _WideMtK1(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, spec, parts, scale_rows, ls_rows):
+        ctx.spec = spec
+        ctx.save_for_backward(parts, scale_rows, ls_rows)
+        return wide_mt_k1_raw(spec, parts, scale_rows, ls_rows)
+
+    @staticmethod
+    def backward(ctx, u):
+        parts, scale_rows, ls_rows = ctx.saved_tensors
+        ds, dl = wide_mt_k1_bwd_raw(ctx.spec, parts, scale_rows, ls_rows, u)
+        return None, None, ds.reshape(scale_rows.shape), dl
+
+
+def wide_mt_k1(spec, parts, scale_rows, ls_rows):
+    """First-column kernel of one task pair over G hyper-parameter rows, d > 8 and P <= 16 (abstract_fast_gp.py:
+    181-191): k1 [G, n], differentiable with respect to the NATURAL scale rows [G] and lengthscale rows [G, d] -- torch
+    chains on through the parameter transforms and the task kernel -- without [G, P, d, n] temporaries or a prod
+    backward (fgp_wide_mt_k1 / fgp_wide_mt_k1_bwd)."""
+    if torch.is_grad_enabled() and (scale_rows.requires_grad or ls_rows.requires_grad):
+        return _WideMtK1.apply(spec, parts, scale_rows, ls_rows)
+    return wide_mt_k1_raw(spec, parts, scale_rows, ls_rows)
+
+
+def wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs=False):
+    """rows[g, t, i] = K_ab(xt[t], z[:, i]) -> [Gk, N, n], or with zip_pairs (N == n) rows[g, t] = K_ab(xt[t], z[:, t])
+    -> [Gk, N] (fgp_wide_mt_rows): xt [N, d] float64 test points, z_dn [d, n] dimension-major (float64 lattice / int64
+    net), hyp [Gk, 1 + d] (scale, lengthscales)."""
+    require_device(xt, "wide_mt_rows")
+    xt = xt.to(torch.float64).contiguous()
+    Nt, d = xt.shape
+    n = z_dn.shape[1]
+    assert z_dn.is_contiguous() and z_dn.shape[0] == d == spec.d
+    assert z_dn.dtype == (torch.float64 if spec.family == LATTICE else torch.int64)
+    hyp = hyp.detach().to(torch.float64).contiguous()
+    Gk = hyp.shape[0]
+    assert hyp.shape == (Gk, 1 + d)
+    args = (d, spec.P, spec.order, spec.coef, spec.add, spec.ind, spec.cc, spec.tbits, N.ptr(hyp), Gk)
+    if zip_pairs:
+        assert Nt == n
+        rows = torch.empty((Gk, Nt), dtype=torch.float64, device=xt.device)
+        N.call("fgp_wide_mt_rows", spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, 1, *args, N.ptr(rows), _stream(xt))
+        return rows
+    rows = torch.empty((Gk, Nt, n), dtype=torch.float64, device=xt.device)
+    for t0 in range(0, Nt, 65535):
+        t1 = min(Nt, t0 + 65535)
+        sub = torch.empty((Gk, t1 - t0, n), dtype=torch.float64, device=xt.device) if Nt > 65535 else rows
+        N.call("fgp_wide_mt_rows", spec.family, N.ptr(xt[t0:t1]), t1 - t0, N.ptr(z_dn), n, 0, *args, N.ptr(sub), _stream(xt))
+        if sub is not rows:
+            rows[:, t0:t1] = sub
+    return rows
+
+
 def mt_factor(lay, lams):
     """Structured LDL^H of G problems' Gram blocks (fgp_mt_factor): lams [G, L] complex128 ->
     (factor [G, L], logdet per frequency class [G, nmin], info [1] int32 device flag)."""

@@ -609,6 +609,46 @@ extern int fgp_wide_post_var_qf(int family, const double* xt, int64_t xt_stride,
                                 const double* hyp, int64_t hyp_stride, const double* wa, int64_t wa_stride, int P,
                                 void* work, double* partial, double* out, void* stream);
 
+/* Addition to ABI 20 -- the task-pair kernel of multitask / derivative-informed GPs for wide d (abstract_fast_gp.py:
+ * 173-191), 9 <= d <= 64 and 1 <= P <= FGP_WIDE_MT_MAX_P derivative multi-index pairs p = p0-major:
+ *   K_ab(x, z) = scale sum_p cc[p] prod_j (ind[p][j] + l_j part[p][j](x, z)),
+ *   part = coef[p][j] B_order[p][j]((x_j - z_j) mod 1)               (lattice; Bernoulli orders 1..8),
+ *          coef[p][j] (add[p][j] + omega_order[p][j](x_j XOR z_j))   (net; Walsh orders 1..4, tbits in 1..63),
+ * cc[p] = c0[p0] c1[p1], ind[p][j] = (beta0[p0][j] + beta1[p1][j] == 0).  order / coef / add / ind [P][d] and cc [P]
+ * are HOST arrays (add may be NULL for lattices); the tables the kernels read are uploaded once per distinct spec and
+ * device, a blocking copy on first use.  The product runs in ascending j, the sum in ascending p, then the scale;
+ * every reduction is fixed-order, so a call repeats bit for bit.
+ * Each entry point validates before any HIP call (also without a device) and names the offending argument: d outside
+ * 9 .. 64, P < 1, a negative size, a null pointer, tbits outside 1 .. 63 for nets, an ind entry other than 0 / 1:
+ * FGP_ERR_INVALID; P > FGP_WIDE_MT_MAX_P or an order outside its range: FGP_ERR_UNSUPPORTED (the caller's torch
+ * formulation covers more pairs).  (`extern` as the entry points above.) */
+#define FGP_WIDE_MT_MAX_P 16
+/* fgp_mt_parts for wide d, written dimension-major: parts[p][j][e], e = i M + k over the (x_i, z_k) pairs, or e = i
+ * over the zipped pairs (zip: N == M).  x [N][d], z [M][d] (float64 lattice points / int64 t-bit net points), row
+ * strides in elements.  The arithmetic of fgp_mt_parts. */
+extern int fgp_wide_mt_parts(int family, const void* x, int64_t x_row_stride, int64_t N, const void* z,
+                             int64_t z_row_stride, int64_t M, int zip, int d, int P, const int* order, const double* coef,
+                             const double* add, int tbits, double* parts, void* stream);
+/* k1[g][i] = scale[g] sum_p cc[p] prod_j (ind[p][j] + ls[g][j] parts[p][j][i]) over G hyper-parameter rows:
+ * parts [P][d][n], scale [G], ls [G][d], k1 [G][n] on the device. */
+extern int fgp_wide_mt_k1(const double* parts, int64_t n, int d, int P, const int* ind, const double* cc,
+                          const double* scale, const double* ls, int G, double* k1, void* stream);
+/* The adjoint of fgp_wide_mt_k1 for the natural scale and lengthscale rows, from u = dL/dk1 [G][n]:
+ *   dscale[g] = sum_i u_gi sum_p cc[p] prod_j f_pj,   dls[g][j] = sum_i u_gi scale_g sum_p cc[p] parts[p][j][i]
+ * prod_{j' != j} f_pj', the leave-one-out products from prefix / suffix products (no divisions: a factor may be 0 or
+ * negative).  1 <= n <= 2^31, G <= 65535; work: fgp_wide_mt_k1_bwd_work doubles. */
+extern int fgp_wide_mt_k1_bwd_work(int64_t n, int d, int P, int G, int64_t* len);
+extern int fgp_wide_mt_k1_bwd(const double* parts, int64_t n, int d, int P, const int* ind, const double* cc,
+                              const double* scale, const double* ls, int G, const double* u, double* dscale, double* dls,
+                              double* work, void* stream);
+/* rows[g][t][i] = K_ab(xt[t], z[:, i]), [Gk][N][n], the parts formed from the points: xt [N][d] float64 test points
+ * (nets: converted to t-bit integers as fgp_wide_kernel_rows does), z dimension-major [d][n] (float64 lattice /
+ * int64 net), hyp device [Gk][1 + d] (scale, lengthscales), N <= 65535.  zip (N == n): rows[g][t] = K_ab(xt[t],
+ * z[:, t]), [Gk][N], any N. */
+extern int fgp_wide_mt_rows(int family, const double* xt, int64_t N, const void* z, int64_t n, int zip, int d, int P,
+                            const int* order, const double* coef, const double* add, const int* ind, const double* cc,
+                            int tbits, const double* hyp, int Gk, double* rows, void* stream);
+
 
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):
  * xb[i - n_min][j] = XOR_{k: bit k of i} C[j][k] XOR shift[j] (t-bit ints), x = xb 2^-t; C [d][mcols] and
