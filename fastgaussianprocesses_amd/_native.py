@@ -121,7 +121,29 @@ class WideFitDesc(ctypes.Structure):
     ]
 
 
+class WideMtPair(ctypes.Structure):
+    """Mirror of fgp_wide_mt_pair (include/fgp_hip.h): one sorted task pair of fgp_wide_mt_fit_desc."""
+    _fields_ = [("parts", _c_vp), ("ind", _c_vp), ("cc", _c_vp), ("P", _c_int), ("conj", _c_int)]
+
+
+class WideMtFitDesc(ctypes.Structure):
+    """Mirror of fgp_wide_mt_fit_desc (include/fgp_hip.h, an addition to ABI 20)."""
+    _fields_ = [
+        ("family", _c_int), ("d", _c_int), ("B", _c_int),
+        ("layout", MtLayout), ("task", _c_int * 16),
+        ("T_all", _c_int), ("rank", _c_int), ("dl", _c_int),
+        ("pair", WideMtPair * 136), ("y", _c_vp), ("raw", _c_vp),
+        ("vtask_exp", _c_int),
+        ("rg_scale", _c_int), ("rg_ls", _c_int), ("rg_noise", _c_int), ("rg_factor", _c_int), ("rg_vtask", _c_int),
+        ("rprop_prev", _c_vp), ("rprop_step", _c_vp), ("lr", _c_dbl),
+        ("eta_minus", _c_dbl), ("eta_plus", _c_dbl), ("step_min", _c_dbl), ("step_max", _c_dbl),
+        ("logdet_weight", _c_dbl), ("mll_const", _c_dbl),
+        ("loss_hist", _c_vp), ("raw_hist", _c_vp), ("grad_out", _c_vp), ("work", _c_vp),
+    ]
+
+
 _P_NLL = ctypes.POINTER(NllDesc)
+_P_WIDEMTFIT = ctypes.POINTER(WideMtFitDesc)
 _P_WIDEFIT = ctypes.POINTER(WideFitDesc)
 _P_MTFIT = ctypes.POINTER(MtFitDesc)
 _P_MT = ctypes.POINTER(MtLayout)
@@ -221,6 +243,9 @@ _SIGNATURES = {
                            _c_vp],
     "fgp_wide_mt_rows": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd, _c_pd, _c_pi, _c_pd,
                          _c_int, _c_vp, _c_int, _c_vp, _c_vp],
+    # addition to ABI 20: the device-resident fit loop of wide multitask / derivative-informed GPs
+    "fgp_wide_mt_fit_work": [_P_WIDEMTFIT, _c_pl],
+    "fgp_wide_mt_fit_run": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
 }
 
 

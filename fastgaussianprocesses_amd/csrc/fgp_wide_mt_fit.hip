@@ -1,0 +1,523 @@
+// Wide inputs (9 <= d <= 64), multitask / derivative-informed GPs: the device-resident MLL fit loop,
+// fgp_wide_mt_fit_run (include/fgp_hip.h, an addition to ABI 20) -- AbstractGP.fit's iteration (abstract_gp.py:241-296:
+// loss, loss.backward(), torch.optim.Rprop.step()) over _FastInverseLogDetCache's lams and block inverse
+// (util.py:275-370) for ONE eigen-problem of T sorted tasks, as a fixed sequence of plain launches on the caller's
+// stream.  With np = T (T + 1) / 2 sorted pairs (k, l), k <= l, one iteration is
+//
+//   k1        fgp_wide_mt_k1, one call per pair        k1_kl into A at the packed offset of (k, l)      (fgp_wide_mt.hip)
+//   lambda    fgp_fftbr / fgp_fftbr_real / fgp_fwht    one batched call per sorted task k over its T - k rows
+//   lams      k_wide_mt_lams (new)                     K_task[a_k, a_l] (sqrt(n_l) lam^_kl + noise [k == l]), packed
+//   blocks    fgp_mt_factor / fgp_mt_solve / fgp_mt_selinv / fgp_mt_mll_grad                            (fgp_multitask.hip)
+//   contract  k_wide_mt_contract (new)                 g~ = dL/dlambda over lambda; partials of the noise and K_task
+//                                                      gradients, of the norm and of the logdet
+//   u         fgp_ifftbr (real part) / fgp_ifftbr_real / fgp_fwht, batched per k: u = dL/dk1 over k1
+//   gradient  fgp_wide_mt_k1_bwd, one call per pair    into dsl [np][1 + d]
+//   step      k_wide_mt_fit_step (new, one workgroup)  second level of every sum, loss, histories, chain rule to the
+//                                                      raw parameters, Rprop (rprop_update, fgp_nll.h), the natural
+//                                                      scale / lengthscale row of the next k1
+//
+// 3 np + 2 T + 7 entry-point calls per iteration.  No host synchronisation, no device-to-host copy, no atomics, no
+// inter-workgroup hand-off: every kernel reads what a launch before it wrote.  lam^ = lambda, or conj(lambda) where
+// the pair's conj flag is set (task index a_k > a_l: util.py:280-284).  Nets: lambda and g~ are real (the generic
+// loop's .to(complex128) passes the real part of the gradient back).  fgp_wide_mt_k1 / _k1_bwd take their spec by
+// value (no device table, no copy), so validating every pair's spec before the first launch is all the "first use"
+// there is; the transforms' twiddle tables are made on their first call as everywhere else.
+#include <cmath>
+#include <cstdint>
+
+#include "fgp_common.h"
+#include "fgp_nll.h"
+#include "fgp_runtime.h"
+#include "../../include/fgp_hip.h"
+
+namespace fgp {
+
+constexpr int kWmfT = FGP_MT_MAX_TASKS;
+constexpr int kWmfPairs = FGP_WIDE_MT_FIT_PAIRS;
+constexpr int kWmfMaxParams = 2 + FGP_WIDE_MAX_D + kWmfT * kWmfT + kWmfT;
+
+// what the new kernels need of the problem, by value
+struct WmfLay {
+  int T, np;                       // sorted active tasks, pairs
+  int T_all, rank, vtask_exp;
+  int f_off, v_off, noise_off;     // raw offsets of the task factor, the task noise and the noise
+  int64_t n[kWmfT];                // descending
+  int64_t offk[kWmfT];             // packed offset of pair (k, k); pair (k, l) at offk[k] + (l - k) n[k]
+  int task[kWmfT];                 // task index a_k of sorted task k
+  unsigned long long conj[(kWmfPairs + 63) / 64];   // bit p: pair p's lambda is conjugated
+};
+
+// pair index p (row-major over k <= l) -> (k, l)
+__device__ __forceinline__ void wmf_pair(const WmfLay& m, int p, int& k, int& l) {
+  k = 0;
+  int rem = p;
+  while (rem >= m.T - k) {
+    rem -= m.T - k;
+    ++k;
+  }
+  l = k + rem;
+}
+
+// K_task[a, b] = sum_r F[a, r] F[b, r] + [a == b] v_a from the raw rows (mtg_kt, fgp_multitask.hip; util.py:157-162)
+__device__ __forceinline__ double wmf_kt(const WmfLay& m, const double* __restrict__ raw, int a, int b) {
+  double s = 0.0;
+  for (int r = 0; r < m.rank; ++r) s += raw[m.f_off + a * m.rank + r] * raw[m.f_off + b * m.rank + r];
+  if (a == b) s += m.vtask_exp ? exp(raw[m.v_off + a]) : raw[m.v_off + a];
+  return s;
+}
+
+template <int FAM>
+__device__ __forceinline__ double2 wmf_lam(const void* __restrict__ lam, int64_t e, bool cj) {
+  if constexpr (FAM == 0) {
+    const double2 v = static_cast<const double2*>(lam)[e];
+    return make_double2(v.x, cj ? -v.y : v.y);
+  } else {
+    return make_double2(static_cast<const double*>(lam)[e], 0.0);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// lams[k, l][i] = K_task[a_k, a_l] (sqrt(n_l) lam^_kl[i] + noise [k == l])  (util.py:284-298), thread = entry i of pair
+// p = blockIdx.y.  lam: complex128 (FAM 0) / float64 (FAM 1), packed as the lams.
+template <int FAM>
+__global__ __launch_bounds__(kWG) void k_wide_mt_lams(WmfLay m, const double* __restrict__ raw,
+                                                      const void* __restrict__ lam, double2* __restrict__ lams) {
+  const int p = blockIdx.y;
+  int k, l;
+  wmf_pair(m, p, k, l);
+  const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  if (i >= m.n[k]) return;
+  const int64_t e = m.offk[k] + (int64_t)(l - k) * m.n[k] + i;
+  const bool cj = (m.conj[p >> 6] >> (p & 63)) & 1ull;
+  const double2 v = wmf_lam<FAM>(lam, e, cj);
+  const double rn = sqrt((double)m.n[l]);
+  double bx = rn * v.x;
+  const double by = rn * v.y;
+  if (k == l) bx += exp(raw[m.noise_off]);
+  const double kt = wmf_kt(m, raw, m.task[k], m.task[l]);
+  lams[e] = make_double2(bx * kt, by * kt);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Pair p = blockIdx.y < np, entries [blockIdx.x kWG, +kWG): with g = dL/dlams (torch's convention dL/dRe + i dL/dIm),
+//   lam[e]             = g~ = K_task sqrt(n_l) g, conjugated by the pair's flag (FAM 1: its real part)
+//   part[p][0][blk]    = sum_i Re g[i]                                               (diagonal pairs: d/dnoise / K_task)
+//   part[p][1][blk]    = sum_i Re(conj(g[i]) (sqrt(n_l) lam^[i] + noise [k == l]))   (dL/dK_task[a_k, a_l])
+// blockIdx.y == np: part[np][0][blk] = this workgroup's share of sum_b Re(conj(y_b) z_b), part[np][1][blk] of the
+// classes' logdet.  A workgroup past its pair's n_k writes nothing, and the step reads none of its partials.
+template <int FAM>
+__global__ __launch_bounds__(kWG) void k_wide_mt_contract(WmfLay m, const double* __restrict__ raw,
+                                                          const double2* __restrict__ glp, void* __restrict__ lam,
+                                                          const double2* __restrict__ y, const double2* __restrict__ z,
+                                                          int64_t yz_len, const double* __restrict__ logdet, int nbx,
+                                                          double* __restrict__ part) {
+  __shared__ double red[kWG / 64];
+  const int p = blockIdx.y;
+  double s0 = 0.0, s1 = 0.0;
+  if (p == m.np) {
+    const int64_t t0 = (int64_t)blockIdx.x * kWG + threadIdx.x, nt = (int64_t)nbx * kWG;
+    for (int64_t e = t0; e < yz_len; e += nt) {
+      const double2 yv = y[e], zv = z[e];
+      s0 = __builtin_fma(yv.x, zv.x, __builtin_fma(yv.y, zv.y, s0));
+    }
+    for (int64_t j = t0; j < m.n[m.T - 1]; j += nt) s1 += logdet[j];
+  } else {
+    int k, l;
+    wmf_pair(m, p, k, l);
+    if ((int64_t)blockIdx.x * kWG >= m.n[k]) return;
+    const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
+    if (i < m.n[k]) {
+      const int64_t e = m.offk[k] + (int64_t)(l - k) * m.n[k] + i;
+      const bool cj = (m.conj[p >> 6] >> (p & 63)) & 1ull;
+      const double2 v = wmf_lam<FAM>(lam, e, cj);
+      const double2 g = glp[e];
+      const double rn = sqrt((double)m.n[l]);
+      double bx = rn * v.x;
+      const double by = rn * v.y;
+      if (k == l) bx += exp(raw[m.noise_off]);
+      const double f = wmf_kt(m, raw, m.task[k], m.task[l]) * rn;
+      s0 = g.x;
+      s1 = __builtin_fma(g.x, bx, g.y * by);
+      if constexpr (FAM == 0) static_cast<double2*>(lam)[e] = make_double2(f * g.x, cj ? -(f * g.y) : f * g.y);
+      else static_cast<double*>(lam)[e] = f * g.x;
+    }
+  }
+  s0 = block_sum(s0, red);
+  s1 = block_sum(s1, red);
+  if (threadIdx.x == 0) {
+    part[((int64_t)p * 2 + 0) * nbx + blockIdx.x] = s0;
+    part[((int64_t)p * 2 + 1) * nbx + blockIdx.x] = s1;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The step, one workgroup.  raw = [scale, dl lengthscales, noise, task factor T_all x rank, task noise T_all].
+//   mode 0  the natural scale / lengthscale row of the current raw parameters, the constant gradient rows of
+//           fgp_mt_mll_grad (gn [B] = 1/2, gl = 1/2 w) and the cleared info flag, before the first k1 of a run
+//           (init: a new fit's Rprop state prev = 0, step = lr)
+//   mode 1  sums, loss, history rows, gradient: the evaluation without an update
+//   mode 2  the same, the Rprop step of the blocks that require a gradient, and the natural row of the new parameters
+// Sums: level 1 = the per-workgroup partials of k_wide_mt_contract / the per-pair totals of fgp_wide_mt_k1_bwd, level 2
+// here -- a lane over every kWG-th partial in ascending order, then block_sum's fixed tree; the pairs in ascending order.
+struct WmfStep {
+  Fit f;
+  WmfLay lay;
+  int d, dl, B, nbx;
+  int rg_factor, rg_vtask;
+  double w, lr;
+  const double* part;        // [np + 1][2][nbx]
+  const double* dsl;         // [np][1 + d]   dL/dscale, dL/dl_j of every pair
+  double* nat;               // [1 + d]       natural scale, lengthscales
+  double* gn;                // [B], then gl [1]
+  int* info;
+};
+
+__global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, int mode, int init) {
+  __shared__ double red[kWG / 64];
+  __shared__ double tot[2 * (kWmfPairs + 1)];     // [p][0 / 1]: the second-level sums of part
+  __shared__ double dsum[1 + FGP_WIDE_MAX_D];     // sum over the pairs of dsl
+  __shared__ double grad[kWmfMaxParams];
+  const int tid = threadIdx.x;
+  const Fit& f = s.f;
+  const WmfLay& m = s.lay;
+  const int d = s.d, dl = s.dl, np = m.np, n_params = f.n_params;
+  if (mode != 0) {
+    for (int p = 0; p <= np; ++p) {
+      int k = 0, l = 0;
+      int64_t cnt = s.nbx;
+      if (p < np) {
+        wmf_pair(m, p, k, l);
+        cnt = (m.n[k] + kWG - 1) / kWG;
+      }
+      for (int q = 0; q < 2; ++q) {
+        if (p < np && q == 0 && k != l) continue;        // Re g sums: the diagonal pairs only
+        const double* pq = s.part + ((int64_t)p * 2 + q) * s.nbx;
+        double a = 0.0;
+        for (int64_t c = tid; c < cnt; c += kWG) a += pq[c];
+        a = block_sum(a, red);
+        if (tid == 0) tot[2 * p + q] = a;
+      }
+    }
+    if (tid <= d) {
+      double a = 0.0;
+      for (int p = 0; p < np; ++p) a += s.dsl[(int64_t)p * (1 + d) + tid];
+      dsum[tid] = a;
+    }
+    __syncthreads();
+    // the raw gradient of every parameter, before any parameter moves (the task-factor rows read one another)
+    for (int x = tid; x < n_params; x += kWG) {
+      double gs = 0.0;
+      if (x == 0) {
+        gs = s.nat[0] * dsum[0];                                         // exp transforms: d nat / d raw = nat
+      } else if (x < m.noise_off) {
+        const int j = x - 1;
+        if (dl == d) {
+          gs = s.nat[1 + j] * dsum[1 + j];
+        } else {                                                          // one lengthscale: the sum over j, ascending
+          double a = 0.0;
+          for (int jj = 0; jj < d; ++jj) a += dsum[1 + jj];
+          gs = s.nat[1] * a;
+        }
+      } else if (x == m.noise_off) {
+        double a = 0.0;
+        for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k) a += wmf_kt(m, f.raw, m.task[k], m.task[k]) * tot[2 * p];
+        gs = exp(f.raw[x]) * a;
+      } else if (x < m.v_off) {
+        // K_task[a, b] = sum_r F[a, r] F[b, r] + [a == b] v_a:  dF[c, r] += g_ab (F[b, r] [a == c] + F[a, r] [b == c])
+        const int u = x - m.f_off, c = u / m.rank, r = u - c * m.rank;
+        for (int k = 0, p = 0; k < m.T; ++k) {
+          const int a = m.task[k];
+          for (int l = k; l < m.T; ++l, ++p) {
+            const int b = m.task[l];
+            const double gv = tot[2 * p + 1];
+            if (a == c) gs += gv * f.raw[m.f_off + b * m.rank + r];
+            if (b == c) gs += gv * f.raw[m.f_off + a * m.rank + r];
+          }
+        }
+      } else {
+        const int c = x - m.v_off;
+        for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k)
+          if (m.task[k] == c) gs += m.vtask_exp ? tot[2 * p + 1] * exp(f.raw[x]) : tot[2 * p + 1];
+      }
+      grad[x] = gs;
+    }
+    if (tid == 0) {
+      double* lh = f.loss_hist + (int64_t)iter * 3;
+      const double t1 = tot[2 * np], t2 = s.w * tot[2 * np + 1];
+      lh[0] = 0.5 * (t1 + t2) + f.mll_const;
+      lh[1] = t1;
+      lh[2] = t2;
+    }
+    __syncthreads();
+    for (int x = tid; x < n_params; x += kWG) {
+      const double gp = grad[x];
+      f.raw_hist[(int64_t)iter * n_params + x] = f.raw[x];
+      f.grad_out[x] = gp;
+      int rg;
+      if (x == 0) rg = f.scale_rg;
+      else if (x < m.noise_off) rg = f.ls_rg;
+      else if (x == m.noise_off) rg = f.noise_rg;
+      else if (x < m.v_off) rg = s.rg_factor;
+      else rg = s.rg_vtask;
+      if (mode == 2 && rg) rprop_update(f, x, gp);
+    }
+    if (mode != 2) return;
+    __syncthreads();
+  } else {
+    if (init)
+      for (int x = tid; x < n_params; x += kWG) {
+        f.prev[x] = 0.0;
+        f.step[x] = s.lr;
+      }
+    for (int b = tid; b <= s.B; b += kWG) s.gn[b] = b < s.B ? 0.5 : 0.5 * s.w;
+    if (tid == 0) s.info[0] = 0;
+  }
+  if (tid == 0) s.nat[0] = exp(f.raw[0]);
+  for (int j = tid; j < d; j += kWG) s.nat[1 + j] = exp(f.raw[1 + (dl == d ? j : 0)]);
+}
+
+// ------------------------------------------------------------------------------------------------ host side
+struct WmfPlan {
+  WmfLay lay;
+  bool lat;
+  int nbx;
+  int n_params;
+  int64_t L, rn;                                   // packed length, R nmin
+  int log2n[kWmfT];
+  // byte offsets into work
+  size_t o_nat, o_gn, o_info, o_dsl, o_a, o_b, o_w, o_lams, o_fac, o_zinv, o_glp, o_z, o_ld, o_part, o_pb, bytes;
+};
+
+static size_t wmf_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
+  if (!a) return set_error(kErrInvalid, "%s: null pointer: desc", fn);
+  if (a->d <= FGP_MAX_D || a->d > FGP_WIDE_MAX_D)
+    return set_error(kErrInvalid, "%s: d=%d outside %d..%d", fn, a->d, FGP_MAX_D + 1, FGP_WIDE_MAX_D);
+  if (a->family != FGP_FAMILY_LATTICE && a->family != FGP_FAMILY_NET)
+    return set_error(kErrInvalid, "%s: bad family %d", fn, a->family);
+  const int T = a->layout.T;
+  if (T < 1 || T > FGP_MT_MAX_TASKS)
+    return set_error(kErrInvalid, "%s: T=%d (layout.T) outside 1..%d", fn, T, FGP_MT_MAX_TASKS);
+  p = WmfPlan{};
+  WmfLay& m = p.lay;
+  m.T = T;
+  m.np = T * (T + 1) / 2;
+  int64_t L = 0, rn = 0;
+  for (int k = 0; k < T; ++k) {
+    const int64_t nk = a->layout.n[k];
+    if (nk < 1 || (nk & (nk - 1)) || nk > ((int64_t)1 << kMaxLog2N))
+      return set_error(kErrInvalid, "%s: n[%d]=%lld is not a power of two in 1..2^%d", fn, k, (long long)nk, kMaxLog2N);
+    if (k > 0 && nk > a->layout.n[k - 1])
+      return set_error(kErrInvalid, "%s: n[%d]=%lld above n[%d]: the tasks are not sorted by n descending", fn, k,
+                       (long long)nk, k - 1);
+    m.n[k] = nk;
+    m.offk[k] = L;
+    L += nk * (T - k);
+    rn += nk;
+    int lg = 0;
+    while (((int64_t)1 << lg) < nk) ++lg;
+    p.log2n[k] = lg;
+  }
+  if (rn / m.n[T - 1] > FGP_MT_MAX_ROWS)
+    return set_error(kErrUnsupported, "%s: n spread too wide (%lld block rows)", fn, (long long)(rn / m.n[T - 1]));
+  if (a->B < 1) return set_error(kErrInvalid, "%s: B=%d (at least one data vector)", fn, a->B);
+  if (a->dl != 1 && a->dl != a->d) return set_error(kErrInvalid, "%s: dl=%d not in {1, d=%d}", fn, a->dl, a->d);
+  if (a->rank < 0 || a->rank > FGP_MT_MAX_TASKS)
+    return set_error(kErrInvalid, "%s: rank=%d outside 0..%d", fn, a->rank, FGP_MT_MAX_TASKS);
+  if (a->T_all < T || a->T_all > FGP_MT_MAX_TASKS)
+    return set_error(kErrInvalid, "%s: T_all=%d outside T=%d..%d", fn, a->T_all, T, FGP_MT_MAX_TASKS);
+  for (int k = 0; k < T; ++k) {
+    if (a->task[k] < 0 || a->task[k] >= a->T_all)
+      return set_error(kErrInvalid, "%s: task[%d]=%d outside 0..T_all-1", fn, k, a->task[k]);
+    m.task[k] = a->task[k];
+  }
+  for (int q = 0; q < m.np; ++q) {
+    if (a->pair[q].P < 1) return set_error(kErrInvalid, "%s: pair[%d].P=%d (at least 1 multi-index pair)", fn, q, a->pair[q].P);
+    if (a->pair[q].P > FGP_WIDE_MT_MAX_P)
+      return set_error(kErrUnsupported, "%s: pair[%d].P=%d above %d (the generic loop covers more)", fn, q, a->pair[q].P,
+                       FGP_WIDE_MT_MAX_P);
+    if (a->pair[q].conj) m.conj[q >> 6] |= 1ull << (q & 63);
+  }
+  m.T_all = a->T_all;
+  m.rank = a->rank;
+  m.vtask_exp = a->vtask_exp != 0;
+  m.noise_off = 1 + a->dl;
+  m.f_off = m.noise_off + 1;
+  m.v_off = m.f_off + a->T_all * a->rank;
+  p.n_params = m.v_off + a->T_all;
+  p.lat = a->family == FGP_FAMILY_LATTICE;
+  p.L = L;
+  p.rn = rn;
+  p.nbx = (int)((m.n[0] + kWG - 1) / kWG);
+  const size_t B = (size_t)a->B, d = (size_t)a->d, np = (size_t)m.np;
+  size_t o = 0;
+  p.o_nat = o, o += wmf_align(8 * (1 + d));
+  p.o_gn = o, o += wmf_align(8 * (B + 1));
+  p.o_info = o, o += 256;
+  p.o_dsl = o, o += wmf_align(8 * np * (1 + d));
+  p.o_a = o, o += wmf_align(8 * (size_t)L);                              // k1, then u = dL/dk1
+  p.o_b = o, o += wmf_align((p.lat ? 16 : 8) * (size_t)L);               // lambda, then g~
+  p.o_w = o, o += p.lat ? wmf_align(16 * (size_t)L) : 0;                 // the lattice transforms' scratch
+  p.o_lams = o, o += wmf_align(16 * (size_t)L);
+  p.o_fac = o, o += wmf_align(16 * (size_t)L);
+  p.o_zinv = o, o += wmf_align(16 * (size_t)L);
+  p.o_glp = o, o += wmf_align(16 * (size_t)L);
+  p.o_z = o, o += wmf_align(16 * B * (size_t)rn);
+  p.o_ld = o, o += wmf_align(8 * (size_t)m.n[T - 1]);
+  p.o_part = o, o += wmf_align(8 * (np + 1) * 2 * (size_t)p.nbx);
+  p.o_pb = o, o += wmf_align(8 * (1 + d) * (size_t)p.nbx);               // fgp_wide_mt_k1_bwd's partials (G = 1)
+  p.bytes = o;
+  return kOk;
+}
+
+static int wmf_run(const fgp_wide_mt_fit_desc* a, const WmfPlan& p, int iter0, int iters, int final_no_update,
+                   hipStream_t st) {
+  const WmfLay& m = p.lay;
+  const int T = m.T, np = m.np, d = a->d;
+  char* w = static_cast<char*>(a->work);
+  double* nat = reinterpret_cast<double*>(w + p.o_nat);
+  double* gn = reinterpret_cast<double*>(w + p.o_gn);
+  int* info = reinterpret_cast<int*>(w + p.o_info);
+  double* dsl = reinterpret_cast<double*>(w + p.o_dsl);
+  double* A = reinterpret_cast<double*>(w + p.o_a);
+  char* Bf = w + p.o_b;
+  void* W = p.lat ? static_cast<void*>(w + p.o_w) : nullptr;
+  double2* lams = reinterpret_cast<double2*>(w + p.o_lams);
+  double2* fac = reinterpret_cast<double2*>(w + p.o_fac);
+  double2* zinv = reinterpret_cast<double2*>(w + p.o_zinv);
+  double2* glp = reinterpret_cast<double2*>(w + p.o_glp);
+  double2* z = reinterpret_cast<double2*>(w + p.o_z);
+  double* logdet = reinterpret_cast<double*>(w + p.o_ld);
+  double* part = reinterpret_cast<double*>(w + p.o_part);
+  double* pb = reinterpret_cast<double*>(w + p.o_pb);
+  const size_t esz = p.lat ? 16 : 8;                                     // bytes of a lambda element
+  WmfStep s{};
+  s.f.n_params = p.n_params;
+  s.f.raw = a->raw;
+  s.f.prev = a->rprop_prev;
+  s.f.step = a->rprop_step;
+  s.f.grad_out = a->grad_out;
+  s.f.loss_hist = a->loss_hist;
+  s.f.raw_hist = a->raw_hist;
+  s.f.scale_rg = a->rg_scale, s.f.ls_rg = a->rg_ls, s.f.noise_rg = a->rg_noise;
+  s.f.mll_const = a->mll_const;
+  s.f.eta_minus = a->eta_minus, s.f.eta_plus = a->eta_plus, s.f.step_min = a->step_min, s.f.step_max = a->step_max;
+  s.lay = m;
+  s.d = d, s.dl = a->dl, s.B = a->B, s.nbx = p.nbx;
+  s.rg_factor = a->rg_factor, s.rg_vtask = a->rg_vtask;
+  s.w = a->logdet_weight, s.lr = a->lr;
+  s.part = part, s.dsl = dsl, s.nat = nat, s.gn = gn, s.info = info;
+  const Switches sw = read_switches();
+  const fgp_mt_layout* lay = &a->layout;
+  const double2* y = static_cast<const double2*>(a->y);
+  auto step = [&](int iter, int mode, int init) {
+    k_wide_mt_fit_step<<<1, kWG, 0, st>>>(s, iter, mode, init);
+    return check_launch("k_wide_mt_fit_step");
+  };
+  int rc = step(0, 0, iter0 == 0 && a->lr > 0.0);
+  for (int it = 0; it < iters && rc == kOk; ++it) {
+    // k1 of every pair into A at the pair's packed offset: the pairs that share k lie contiguously
+    for (int k = 0, q = 0; k < T && rc == kOk; ++k)
+      for (int l = k; l < T && rc == kOk; ++l, ++q)
+        rc = fgp_wide_mt_k1(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
+                            A + m.offk[k] + (int64_t)(l - k) * m.n[k], st);
+    // lambda = ft(k1), stable (AbstractFastGP.ft), the T - k rows of sorted task k in one call
+    for (int k = 0; k < T && rc == kOk; ++k) {
+      const int64_t n = m.n[k], rows = T - k;
+      const int lg = p.log2n[k];
+      double* in = A + m.offk[k];
+      void* out = Bf + esz * (size_t)m.offk[k];
+      if (!p.lat) rc = fgp_fwht(in, n, static_cast<double*>(out), rows, lg, 1, st);
+      else if (use_r2c(sw, true, lg)) rc = fgp_fftbr_real(in, n, out, W, rows, lg, st);
+      else rc = fgp_fftbr(in, n, 1, out, rows, lg, 1, st);
+    }
+    if (rc != kOk) break;
+    const dim3 gl((unsigned)p.nbx, (unsigned)np), gc((unsigned)p.nbx, (unsigned)np + 1);
+    if (p.lat) k_wide_mt_lams<0><<<gl, kWG, 0, st>>>(m, a->raw, Bf, lams);
+    else k_wide_mt_lams<1><<<gl, kWG, 0, st>>>(m, a->raw, Bf, lams);
+    rc = check_launch("k_wide_mt_lams");
+    // the structured factor, the solves of the B vectors, the selected inverse and dL/dlams (fgp_multitask.hip); a
+    // non-positive pivot sets info and counts as log|pivot|, as in the generic loop and MtGeneralEngine
+    if (rc == kOk) rc = fgp_mt_factor(lay, lams, 1, fac, logdet, info, st);
+    if (rc == kOk) rc = fgp_mt_solve(lay, fac, 1, y, p.rn, a->B, z, st);
+    if (rc == kOk) rc = fgp_mt_selinv(lay, fac, 1, zinv, st);
+    if (rc == kOk) rc = fgp_mt_mll_grad(lay, zinv, z, gn, gn + a->B, a->B, 1, glp, st);
+    if (rc != kOk) break;
+    if (p.lat) k_wide_mt_contract<0><<<gc, kWG, 0, st>>>(m, a->raw, glp, Bf, y, z, (int64_t)a->B * p.rn, logdet, p.nbx, part);
+    else k_wide_mt_contract<1><<<gc, kWG, 0, st>>>(m, a->raw, glp, Bf, y, z, (int64_t)a->B * p.rn, logdet, p.nbx, part);
+    rc = check_launch("k_wide_mt_contract");
+    // u = dL/dk1: the adjoint transform of g~ (lattice: the real part), batched as the forward
+    for (int k = 0; k < T && rc == kOk; ++k) {
+      const int64_t n = m.n[k], rows = T - k;
+      const int lg = p.log2n[k];
+      double* out = A + m.offk[k];
+      void* in = Bf + esz * (size_t)m.offk[k];
+      if (!p.lat) rc = fgp_fwht(static_cast<const double*>(in), n, out, rows, lg, 1, st);
+      else if (use_r2c(sw, true, lg)) rc = fgp_ifftbr_real(in, n, nullptr, 0, out, n, W, rows, lg, st);
+      else rc = fgp_ifftbr(in, n, out, 1, W, rows, lg, 1, st);
+    }
+    for (int k = 0, q = 0; k < T && rc == kOk; ++k)
+      for (int l = k; l < T && rc == kOk; ++l, ++q)
+        rc = fgp_wide_mt_k1_bwd(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
+                                A + m.offk[k] + (int64_t)(l - k) * m.n[k], dsl + (int64_t)q * (1 + d),
+                                dsl + (int64_t)q * (1 + d) + 1, pb, st);
+    if (rc != kOk) break;
+    const bool last = it + 1 == iters;
+    rc = step(iter0 + it, (last && final_no_update) ? 1 : 2, 0);
+  }
+  return rc;
+}
+
+}  // namespace fgp
+
+using namespace fgp;
+
+extern "C" {
+
+int fgp_wide_mt_fit_work(const fgp_wide_mt_fit_desc* desc, int64_t* bytes) {
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_work", desc, p);
+  if (rc != kOk) return rc;
+  if (!bytes) return set_error(kErrInvalid, "fgp_wide_mt_fit_work: null pointer: bytes");
+  *bytes = (int64_t)p.bytes;
+  return kOk;
+}
+
+int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {
+  static const char* fn = "fgp_wide_mt_fit_run";
+  WmfPlan p;
+  int rc = wmf_plan(fn, desc, p);
+  if (rc != kOk) return rc;
+  const struct {
+    const void* ptr;
+    const char* name;
+  } ptrs[] = {{desc->y, "y"},
+              {desc->raw, "raw"},
+              {desc->rprop_prev, "rprop_prev"},
+              {desc->rprop_step, "rprop_step"},
+              {desc->loss_hist, "loss_hist"},
+              {desc->raw_hist, "raw_hist"},
+              {desc->grad_out, "grad_out"},
+              {desc->work, "work"}};
+  for (const auto& q : ptrs)
+    if (!q.ptr) return set_error(kErrInvalid, "%s: null pointer: %s", fn, q.name);
+  for (int q = 0; q < p.lay.np; ++q) {
+    const fgp_wide_mt_pair& pr = desc->pair[q];
+    if (!pr.parts) return set_error(kErrInvalid, "%s: null pointer: pair[%d].parts", fn, q);
+    if (!pr.ind) return set_error(kErrInvalid, "%s: null pointer: pair[%d].ind", fn, q);
+    if (!pr.cc) return set_error(kErrInvalid, "%s: null pointer: pair[%d].cc", fn, q);
+    // every pair's spec is checked here, before the first launch (fgp_wide_mt_k1 takes it by value: nothing to upload)
+    for (int e = 0; e < pr.P * desc->d; ++e)
+      if (pr.ind[e] != 0 && pr.ind[e] != 1)
+        return set_error(kErrInvalid, "%s: pair[%d].ind[%d][%d]=%d is not 0 or 1", fn, q, e / desc->d, e % desc->d, pr.ind[e]);
+  }
+  if (iters < 0) return set_error(kErrInvalid, "%s: iters=%d negative", fn, iters);
+  if (iter0 < 0) return set_error(kErrInvalid, "%s: iter0=%d negative", fn, iter0);
+  if (((uintptr_t)desc->y | (uintptr_t)desc->work) & 15)
+    return set_error(kErrInvalid, "%s: y and work must be 16-byte aligned", fn);
+  if (iters == 0) return kOk;
+  return wmf_run(desc, p, iter0, iters, final_no_update, (hipStream_t)stream);
+}
+
+}  // extern "C"

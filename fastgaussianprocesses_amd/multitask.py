@@ -14,6 +14,8 @@ Where the work runs:
   * the T x T block-eigenvalue inverse (util.py:275-337), its solves,
     logdet and the MLL gradient                                      -> fgp_mt_factor / fgp_mt_solve /
                                                                        fgp_mt_selinv / fgp_mt_mll_grad
+  * at 9 <= d <= 64 under FGP_WIDE_FIT_DEVICE=1: the whole MLL fit iteration (first columns, transforms,
+    blocks, gradients, Rprop)                                         -> fgp_wide_mt_fit_run (WideMtEngine)
   * kernel-from-parts products, the task kernel F F^T + diag(v), the packing of the eigenvalue
     blocks and the optimizer step: torch ops on the device (autograd carries the hyper-parameter
     gradients through them and through the HIP transforms).
@@ -439,6 +441,29 @@ class MultiTaskFastGP(AbstractFastGP):
         return (1, int(self.raw_lengthscales.shape[-1]), 1,
                 int(self.raw_factor_task_kernel.shape[-1]) * self.num_tasks, self.num_tasks)
 
+    def _mt_wide_ok(self):
+        """The device-resident MLL fit at 9 <= d <= 64 (fgp_wide_mt_fit_run: WideMtEngine) applies: the fused wide
+        entry points (FGP_WIDE_FUSED not 0) with every task pair's spec fused (at most 16 derivative multi-index
+        pairs), exp transforms for scale / lengthscales / noise, the identity for the task factor and exp or the
+        identity for the task noise, no parameter batch, the plain nugget, and data in at least one task."""
+        if not ops._wide(self.d) or self.d > N.WIDE_MAX_D or not ops.wide_fused():
+            return False
+        act = [l for l in range(self.num_tasks) if self._ns[l] > 0]
+        if not act or len(act) > N.MT_MAX_TASKS or self.adaptive_nugget:
+            return False
+        if any(self._tfs[k][1] is not _exp for k in ("scale", "lengthscales", "noise")):
+            return False
+        if self.tf_factor_task_kernel is not _identity or self.tf_noise_task_kernel not in (_exp, _identity):
+            return False
+        if self._mt_param_rows() is not None:
+            return False
+        T = self.num_tasks
+        if tuple(self.raw_scale.shape) != (1,) or tuple(self.raw_noise.shape) != (1,) or \
+                tuple(self.raw_lengthscales.shape) not in ((1,), (self.d,)) or self.raw_factor_task_kernel.dim() != 2 or \
+                self.raw_factor_task_kernel.shape[0] != T or tuple(self.raw_noise_task_kernel.shape) != (T,):
+            return False
+        return all(self._wide_pair_spec(min(a, b), max(a, b)) is not None for a in act for b in act)
+
     def _mt_spectra(self, n):
         """Pair spectra Phi^{kl}_S = ft(B^{kl}_S) [T (T+1)/2, 2^d, n] (pairs k <= l row-major): with the
         derivative parts of get_k1parts(k, l) (abstract_fast_gp.py:173-180) and _kernel_from_parts'
@@ -513,7 +538,10 @@ class MultiTaskFastGP(AbstractFastGP):
 
     def _fused_engine(self, iterations, lr, ysq=None, d_out=None, loss_metric="MLL", cv_weight=1.0):
         """FusedMLL in multitask spectral mode (G = 1; loss_metric MLL, GCV (ABI 17) or CV (ABI 18)); the general
-        engine (MtGeneralEngine, MLL) outside its domain (_mt_fused_ok: equal n, fixed task kernel)."""
+        engine (MtGeneralEngine, MLL) outside its domain (_mt_fused_ok: equal n, fixed task kernel); at 9 <= d <= 64
+        the wide engine (WideMtEngine, MLL)."""
+        if ops._wide(self.d):
+            return WideMtEngine(self, lr, min(iterations + 1, 64))       # (_device_fit_args: MLL inside _mt_wide_ok)
         learn = loss_metric != "MLL" and not self._mt_fused_ok() and self._mt_learn_ok()
         if not self._mt_fused_ok() and not learn:
             return MtGeneralEngine(self, lr, min(iterations + 1, 64))
@@ -855,13 +883,18 @@ class MultiTaskFastGP(AbstractFastGP):
         return sum(self._ns) > 0
 
     def _device_fit_args(self, loss_metric, optimizer, masks, cv_weights):
-        """The MLL on the device inside _mt_fused_ok or _mt_general_ok; GCV / CV of T tasks with equal n and a fixed or
+        """The MLL on the device inside _mt_fused_ok or _mt_general_ok, or inside _mt_wide_ok under
+        FGP_WIDE_FIT_DEVICE=1; GCV / CV of T tasks with equal n and a fixed or
         a learned task kernel (k_mt_spec_iter's GCV / CV variants + k_spec_loss_step, ABI 17 / 18; util.py:371-394,
         abstract_gp.py:242-272) unless FGP_ALT_LOSS_DEVICE=0."""
         if optimizer is not None or masks is not None:
             return None
         if loss_metric == "MLL":
-            return {} if self._mt_fused_ok() or self._mt_general_ok() else None
+            if self._mt_fused_ok() or self._mt_general_ok():
+                return {}
+            # 9 <= d <= 64: opt-in, the switch of a single wide GP's fit (default: the generic autograd loop)
+            wide = os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1" and self._mt_wide_ok()
+            return {} if wide else None
         ok = (self._mt_fused_ok() or self._mt_learn_ok()) and os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
         if loss_metric == "CV":
             # (one task: the reference's inv_diag is the single-task formula without the noise, util.py:383-386; a
@@ -1208,3 +1241,78 @@ class MtGeneralEngine(FitEngine):
         FF = FF.reshape(FF.shape[:1] + (1,) * (nb - FF.dim()) + FF.shape[1:])
         V = V.reshape(V.shape[:1] + (1,) * (nb - V.dim()) + V.shape[1:])
         return FF + V
+
+
+class WideMtEngine(MtGeneralEngine):
+    """Device-resident MLL fit of a multitask / derivative-informed GP at 9 <= d <= 64 (include/fgp_hip.h, an addition
+    to ABI 20: fgp_wide_mt_fit_run): MtGeneralEngine's raw vector, histories and task-kernel hooks, with the pair
+    spectra (which do not exist at these d) replaced by every sorted pair's dimension-major first-column parts and its
+    fused spec; lambda is transformed from k1 in every iteration."""
+
+    def __init__(self, gp, lr, max_iters):
+        self.gp = gp
+        self.device = dev = gp.device
+        lo = _Layout(gp._ns)
+        self.lo = lo
+        T, d = gp.num_tasks, gp.d
+        Y = lo.pack([gp.get_ytilde(l).to(torch.complex128) for l in range(T)])
+        B = int(np.prod(tuple(Y.shape[:-1]))) if Y.dim() > 1 else 1
+        self.y = Y.reshape(B, -1).resolve_conj().contiguous()
+        self.G, self.B, self.rows = 1, B, None
+        dl = int(gp.raw_lengthscales.shape[-1])
+        r = int(gp.raw_factor_task_kernel.shape[-1])
+        self.sizes = gp._mt_row_widths()
+        self.raw = torch.cat([gp.raw_scale.detach().reshape(-1), gp.raw_lengthscales.detach().reshape(-1),
+                              gp.raw_noise.detach().reshape(-1), gp.raw_factor_task_kernel.detach().reshape(-1),
+                              gp.raw_noise_task_kernel.detach().reshape(-1)]).to(dev, torch.float64).contiguous()
+        self.n_params = int(self.raw.numel())
+        st = torch.zeros((3, self.n_params), dtype=torch.float64, device=dev)
+        self.prev, self.step, self.grad = st[0], st[1], st[2]
+        d_out = int(torch.tensor(tuple(gp.shape_batch)).prod()) if len(gp.shape_batch) else 1
+        desc = N.WideMtFitDesc()
+        desc.family, desc.d, desc.B = int(gp._FAMILY), int(d), B
+        desc.layout = lo.lay
+        for k, a in enumerate(lo.active):
+            desc.task[k] = int(a)
+        desc.T_all, desc.rank, desc.dl = int(T), r, dl
+        # sorted pair (k, l), tasks a = active[k], b = active[l]: the reference's lam_kl is get_lam(a, b, n_k) for a <= b
+        # and get_lam(b, a, n_k).conj() otherwise (util.py:280-284; _lams_blocks)
+        self._pairs = []
+        for p, (k, l) in enumerate(lo.pairs):
+            a, b = lo.active[k], lo.active[l]
+            t0, t1 = min(a, b), max(a, b)
+            spec = gp._wide_pair_spec(t0, t1)
+            parts = gp._k1parts_dm(t0, t1, lo.nsrt[k])
+            assert spec is not None and parts.is_contiguous() and tuple(parts.shape) == (spec.P, d, lo.nsrt[k])
+            self._pairs.append((spec, parts))                      # (the host tables and the parts stay alive)
+            pr = desc.pair[p]
+            pr.parts = parts.data_ptr()
+            pr.ind, pr.cc = ctypes.addressof(spec.ind), ctypes.addressof(spec.cc)
+            pr.P, pr.conj = spec.P, int(a > b)
+        desc.y = self.y.data_ptr()
+        desc.raw = self.raw.data_ptr()
+        desc.vtask_exp = int(gp.tf_noise_task_kernel is _exp)
+        desc.rg_scale, desc.rg_ls, desc.rg_noise = (int(gp.raw_scale.requires_grad), int(gp.raw_lengthscales.requires_grad),
+                                                    int(gp.raw_noise.requires_grad))
+        desc.rg_factor, desc.rg_vtask = int(gp.raw_factor_task_kernel.requires_grad), int(gp.raw_noise_task_kernel.requires_grad)
+        desc.rprop_prev, desc.rprop_step, desc.grad_out = self.prev.data_ptr(), self.step.data_ptr(), self.grad.data_ptr()
+        desc.lr = float(lr)
+        desc.eta_minus, desc.eta_plus = RPROP_ETAS
+        desc.step_min, desc.step_max = RPROP_STEPS
+        # one problem's logdet stands for the d_out outputs sharing it (abstract_gp.py:256); the loss is
+        # 1/2 (norm + w logdet) + 1/2 d_out sum(n) log(2 pi)
+        desc.logdet_weight = float(d_out)
+        desc.mll_const = 0.5 * float(mll_constant(d_out, sum(gp._ns)))
+        wb = ctypes.c_int64(0)
+        N.call("fgp_wide_mt_fit_work", desc, ctypes.byref(wb))
+        self.work = torch.empty((max(1, wb.value),), dtype=torch.uint8, device=dev)
+        desc.work = self.work.data_ptr()
+        self.desc = desc
+        self.ensure_history(max_iters)
+
+    def run(self, iter0, iters, final_no_update=False):
+        """Enqueue `iters` iterations writing history rows iter0 .. iter0 + iters - 1 (plain launches on the current
+        stream, no host synchronisation).  iter0 = 0 starts a new fit (Rprop state reset on the device)."""
+        self.ensure_history(iter0 + iters)
+        N.call("fgp_wide_mt_fit_run", self.desc, int(iter0), int(iters), int(bool(final_no_update)),
+               N.stream_ptr(self.device))

@@ -808,6 +808,73 @@ int fgp_mt_fit_work(const fgp_mt_fit_desc* desc, int64_t* bytes);
 /* iterations iter0 .. iter0 + iters - 1 (history rows); with final_no_update the last one evaluates only */
 int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
 
+/* Addition to ABI 20 -- the device-resident MLL fit loop of a multitask / derivative-informed GP on wide inputs
+ * (9 <= d <= 64): fgp_mt_fit_run's problem (ONE eigen-problem: T active tasks sorted by n descending, any power-of-two n
+ * per task, B >= 1 data vectors sharing the hyper-parameters, torch.optim.Rprop) without pair spectra, which do not
+ * exist at these d.  Per iteration, plain launches on the caller's stream with no host synchronisation, no
+ * device-to-host copy, no atomics and no inter-workgroup hand-off, np = T (T + 1) / 2 sorted pairs (k, l), k <= l:
+ *   k1_kl (fgp_wide_mt_k1 per pair, from the natural scale / lengthscale row kept in work), lambda_kl = ft(k1_kl) (the
+ *   stable real-input transforms of AbstractFastGP.ft, one batched call per sorted task k over its T - k rows: the
+ *   bits of get_lam), lams[k, l] = K_task[a_k, a_l] (sqrt(n_l) lam^_kl + noise [k == l]) with lam^ = lambda, or
+ *   conj(lambda) where the pair's conj flag is set, and K_task = F F^T + diag(v) from the raw rows; fgp_mt_factor,
+ *   fgp_mt_solve over the B vectors, fgp_mt_selinv and fgp_mt_mll_grad (dL/dnorm_b = 1/2, dL/dlogdet = 1/2 w; a
+ *   non-positive pivot counts as log|pivot|, as in fgp_mt_fit_run); the contraction kernel (g~ = K_task sqrt(n_l)
+ *   dL/dlams, conjugated by the flag, over lambda; per-workgroup partials of the noise gradient, of every dL/dK_task
+ *   entry, of the norm and of the logdet); u = dL/dk1 = Re of the adjoint transform, batched as the forward;
+ *   fgp_wide_mt_k1_bwd per pair; and the one-workgroup step kernel (the second level of every sum, the pairs added in
+ *   ascending order, loss = 1/2 (sum_b norm_b + w logdet) + mll_const, the history rows, the chain rule through the
+ *   transforms -- the sum over j when dl = 1, dK_task -> F, v -- and rprop_update for the blocks whose rg_* is set).
+ *   3 np + 2 T + 7 entry-point calls per iteration.
+ * raw = [raw_scale, raw_lengthscales (dl in {1, d}), raw_noise, raw_factor_task_kernel (T_all x rank, row-major),
+ *        raw_noise_task_kernel (T_all)]: scale / lengthscales / noise exp-transformed, the factor identity, the task
+ *        noise exp (vtask_exp = 1) or identity (0).  n_params = 2 + dl + T_all rank + T_all.
+ * loss_hist [iters][3] = (loss, sum_b norm_b, w logdet); raw_hist [iters][n_params]; row i of both holds the loss and
+ * the parameters AT iteration i, before its step.  grad_out [n_params]: the raw gradient of the last evaluation.
+ * iter0, iters, final_no_update and lr as fgp_wide_fit_run.  y and work must be 16-byte aligned. */
+#define FGP_WIDE_MT_FIT_PAIRS (FGP_MT_MAX_TASKS * (FGP_MT_MAX_TASKS + 1) / 2)
+typedef struct fgp_wide_mt_pair {
+  const double* parts;        /* device [P][d][n_k] dimension-major parts (fgp_wide_mt_parts) of sorted pair (k, l) */
+  const int* ind;             /* host [P][d], as fgp_wide_mt_k1 takes it */
+  const double* cc;           /* host [P] */
+  int P;                      /* 1 .. FGP_WIDE_MT_MAX_P */
+  int conj;                   /* 1: lambda_kl enters the blocks conjugated (task index a_k > a_l, util.py:280-284) */
+} fgp_wide_mt_pair;
+
+typedef struct fgp_wide_mt_fit_desc {
+  int family, d, B;                   /* B data vectors (the reference's shape_batch, parameters unbatched) */
+  fgp_mt_layout layout;               /* active tasks sorted by n descending */
+  int task[FGP_MT_MAX_TASKS];         /* task index of active (sorted) task k */
+  int T_all, rank, dl;                /* num_tasks, columns of the task factor, lengthscale count (1 or d) */
+  fgp_wide_mt_pair pair[FGP_WIDE_MT_FIT_PAIRS];   /* sorted pair p = (k, l), k <= l, row-major over (k, l) */
+  const void* y;                      /* complex128 [B][R nmin]: ytilde of the sorted tasks, rows concatenated */
+  double* raw;
+  int vtask_exp;
+  int rg_scale, rg_ls, rg_noise, rg_factor, rg_vtask;   /* requires_grad of each parameter tensor */
+  double* rprop_prev;                 /* [n_params] Rprop state (torch.optim.Rprop: prev, step_size) */
+  double* rprop_step;
+  double lr;                          /* > 0: a run with iter0 == 0 starts a new fit (prev = 0, step = lr, set on the
+                                         device); <= 0: the Rprop state is the caller's */
+  double eta_minus, eta_plus, step_min, step_max;
+  double logdet_weight;               /* w = d_out / numel(logdet) (abstract_gp.py:256) */
+  double mll_const;                   /* 1/2 d_out sum(n) log(2 pi), added to 1/2 (norm + w logdet) */
+  double* loss_hist;
+  double* raw_hist;
+  double* grad_out;
+  void* work;                         /* fgp_wide_mt_fit_work bytes */
+} fgp_wide_mt_fit_desc;
+
+/* Bytes of `work`.  Validates the desc's sizes (not its pointers) as fgp_wide_mt_fit_run does. */
+extern int (fgp_wide_mt_fit_work)(const fgp_wide_mt_fit_desc* desc, int64_t* bytes);
+/* Arguments are validated before any HIP call (also without a device), each message naming the field: d outside
+ * 9 .. 64, T (layout.T) outside 1 .. FGP_MT_MAX_TASKS, an n that is not a power of two or not descending, B < 1, dl
+ * not in {1, d}, rank < 0, a null pointer and negative iters return FGP_ERR_INVALID; a pair with P >
+ * FGP_WIDE_MT_MAX_P returns FGP_ERR_UNSUPPORTED.  Every pair's spec is checked there too: fgp_wide_mt_k1 and its
+ * adjoint take it by value, so no iteration uploads anything.  (`extern` as the entry points above, and the names in
+ * parentheses -- the same declarations in C: tests/test_wide_mt_cpu.py takes the `extern int fgp_wide_mt_<name>(`
+ * declarations as the fixed set of the task-pair kernel's entry points.) */
+extern int (fgp_wide_mt_fit_run)(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update,
+                                 void* stream);
+
 /* ABI 15 -- consistency check of the fused spectral fit's last-arriver hand-off (a test hook, no reference
  * counterpart).  enable != 0 arms it for the following fgp_fit_run calls: every wave of the one-launch
  * iteration kernel XORs the bits of the partials it stored into a per-group word (agent-scope atomics, before
