@@ -246,6 +246,8 @@ _SIGNATURES = {
     # addition to ABI 20: the device-resident fit loop of wide multitask / derivative-informed GPs
     "fgp_wide_mt_fit_work": [_P_WIDEMTFIT, _c_pl],
     "fgp_wide_mt_fit_run": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
+    # addition to ABI 20: the multitask posterior variance's quadratic form
+    "fgp_mt_quadform": [_P_MT, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp],
 }
 
 

@@ -186,6 +186,172 @@ __global__ __launch_bounds__(kWG) void k_mt_solve(const double2* __restrict__ fa
   mt_solve_class(fac + g * lay.L + j, lay, v + b * vs + j, out + b * (int64_t)lay.R * nm + j);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Quadratic form v^H Lambda^-1 v = sum_j sum_r |w_rj|^2 / D_rj, w = L^-1 v (fgp_mt_quadform; the posterior variance's
+// k^T K^-1 k by Parseval: no D scaling of the vector, no back substitution, no solution array).  The forward
+// substitution is mt_solve_class's first loop with its order of updates; the pivot enters as k_mt_solve reads it,
+// 1 / D.  A thread takes V vectors of one problem and one class and loads every factor entry once for all of them
+// (the factor is what B / G vectors re-read).  VT = double2 (lattice) or double (net: a real vector against the real
+// parts of the couplings -- the factor of a real symmetric problem has no others).
+//   q[b] = sum_r (ascending rows, per thread)  ->  block_sum over the kWG classes of a workgroup  ->
+//   partial[b][blockIdx class chunk]  ->  k_mt_qf_sum (thread-strided over the chunks, block_sum).
+// Every vector's operations and their order are those of a launch with that vector alone, so out[b] carries the same
+// bits whatever B, V or the other vectors are.
+__device__ __forceinline__ void qf_sub(double2& o, double2 u, double2 w) { o -= cmul_cj(u, w); }
+__device__ __forceinline__ void qf_sub(double& o, double2 u, double w) { o -= u.x * w; }
+__device__ __forceinline__ double qf_abs2(double2 w) { return __builtin_fma(w.x, w.x, w.y * w.y); }
+__device__ __forceinline__ double qf_abs2(double w) { return w * w; }
+
+// workgroup blockIdx.x = (problem g, group of V vectors, class chunk cb), the chunk fastest
+struct QfIdx {
+  int64_t g, i0, j;      // problem, first vector of the group (vector i of problem g is b = g + i G), class
+  int cb, cnt;           // class chunk, vectors of the group that exist (1 .. V)
+  bool active;           // j < nmin
+};
+template <int V>
+__device__ __forceinline__ QfIdx qf_index(const MtLay& lay, int64_t G, int64_t B, int nblk) {
+  QfIdx x;
+  const int64_t nv = B / G, ngv = (nv + V - 1) / V;
+  const int64_t grp = (int64_t)blockIdx.x / nblk;
+  x.cb = (int)((int64_t)blockIdx.x - grp * nblk);
+  x.g = grp / ngv;
+  x.i0 = (grp - x.g * ngv) * V;
+  x.cnt = (int)std::min<int64_t>(V, nv - x.i0);
+  x.j = (int64_t)x.cb * kWG + threadIdx.x;
+  x.active = x.j < lay.nmin;
+  return x;
+}
+
+// the workgroup's sums into partial[b][cb] (inactive threads hold 0; every thread of the workgroup arrives)
+template <int V>
+__device__ __forceinline__ void qf_store(const QfIdx& x, int64_t G, int nblk, const double* acc, double* __restrict__ partial,
+                                         double* red) {
+#pragma unroll
+  for (int u = 0; u < V; ++u) {
+    if (u >= x.cnt) break;                              // uniform over the workgroup
+    const double s = block_sum(acc[u], red);
+    if (threadIdx.x == 0) partial[(x.g + (x.i0 + u) * G) * nblk + x.cb] = s;
+  }
+}
+
+// equal n: R = T rows, one per task, w in registers; v is only read
+template <typename VT, int T, int V>
+__global__ __launch_bounds__(kWG) void k_mt_qf_reg(const double2* __restrict__ fac, int64_t G, MtLay lay,
+                                                   const VT* __restrict__ v, int64_t vs, int64_t B,
+                                                   double* __restrict__ partial, int nblk) {
+  __shared__ double red[kWG / 64];
+  const QfIdx x = qf_index<V>(lay, G, B, nblk);
+  const int64_t nm = lay.nmin;
+  double acc[V];
+#pragma unroll
+  for (int u = 0; u < V; ++u) acc[u] = 0.0;
+  if (x.active) {
+    const double2* F = fac + x.g * lay.L + x.j;
+    VT w[V][T];
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      // (a vector the group does not have: the group's first again, its result is not stored)
+      const VT* vb = v + (x.g + (x.i0 + (u < x.cnt ? u : 0)) * G) * vs + x.j;
+#pragma unroll
+      for (int k = 0; k < T; ++k) w[u][k] = vb[(int64_t)k * nm];
+    }
+#pragma unroll
+    for (int k = 0; k < T; ++k) {
+      // (equal n: pair (k, l) is the (k T - k (k - 1) / 2 + l - k)-th segment of n entries -- lay.off without its loads)
+      const double id = 1.0 / F[(int64_t)(k * T - k * (k - 1) / 2) * nm].x;
+#pragma unroll
+      for (int u = 0; u < V; ++u) acc[u] += qf_abs2(w[u][k]) * id;
+#pragma unroll
+      for (int l = k + 1; l < T; ++l) {
+        const double2 c = F[(int64_t)(k * T - k * (k - 1) / 2 + l - k) * nm];
+#pragma unroll
+        for (int u = 0; u < V; ++u) qf_sub(w[u][l], c, w[u][k]);
+      }
+    }
+  }
+  qf_store<V>(x, G, nblk, acc, partial, red);
+}
+
+// any layout: R rows (unbounded), the substitution in place in v (v is overwritten by w = L^-1 v)
+template <typename VT, int V>
+__global__ __launch_bounds__(kWG) void k_mt_qf_gen(const double2* __restrict__ fac, int64_t G, MtLay lay,
+                                                   VT* __restrict__ v, int64_t vs, int64_t B,
+                                                   double* __restrict__ partial, int nblk) {
+  __shared__ double red[kWG / 64];
+  const QfIdx x = qf_index<V>(lay, G, B, nblk);
+  const int64_t nm = lay.nmin;
+  double acc[V];
+#pragma unroll
+  for (int u = 0; u < V; ++u) acc[u] = 0.0;
+  if (x.active) {
+    const double2* F = fac + x.g * lay.L + x.j;
+    VT* vb = v + (x.g + x.i0 * G) * vs + x.j;           // vector u of the group: vb + u G vs
+    const int64_t us = G * vs;
+    for (int k = 0; k < lay.T; ++k) {
+      const int qk = (int)(lay.n[k] / nm);
+      const double2* Dk = F + lay.off[k * FGP_MT_MAX_TASKS + k];
+      for (int q = 0; q < qk; ++q) {
+        const double id = 1.0 / Dk[(int64_t)q * nm].x;
+        const int64_t rq = (int64_t)(lay.rs[k] + q) * nm;
+        VT wq[V];
+#pragma unroll
+        for (int u = 0; u < V; ++u)
+          if (u < x.cnt) {
+            wq[u] = vb[u * us + rq];
+            acc[u] += qf_abs2(wq[u]) * id;
+          }
+        for (int l = k + 1; l < lay.T; ++l) {
+          const int ql = (int)(lay.n[l] / nm);
+          const double2 c = F[lay.off[k * FGP_MT_MAX_TASKS + l] + (int64_t)q * nm];
+          const int64_t rl = (int64_t)(lay.rs[l] + q % ql) * nm;
+#pragma unroll
+          for (int u = 0; u < V; ++u)
+            if (u < x.cnt) {
+              VT t = vb[u * us + rl];
+              qf_sub(t, c, wq[u]);
+              vb[u * us + rl] = t;
+            }
+        }
+      }
+    }
+  }
+  qf_store<V>(x, G, nblk, acc, partial, red);
+}
+
+// out[b] = sum_c partial[b][c]: one workgroup per vector, a thread over every kWG-th chunk in ascending order, then
+// block_sum's fixed tree (k_sum_chunks of fgp_predict.hip)
+__global__ __launch_bounds__(kWG) void k_mt_qf_sum(const double* __restrict__ partial, int64_t nblk,
+                                                   double* __restrict__ out) {
+  __shared__ double red[kWG / 64];
+  const int64_t b = blockIdx.x;
+  double s = 0.0;
+  for (int64_t c = threadIdx.x; c < nblk; c += kWG) s += partial[b * nblk + c];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) out[b] = s;
+}
+
+// vectors per thread: w takes 4 V T (lattice) / 2 V T (net) of the lane's 512 registers; V = 4 up to 8 tasks and V = 2
+// up to 16 keep w at 128 or fewer; with the loads in flight the kernels allocate 23 .. 202 registers (no spill, two
+// waves per SIMD or more)
+constexpr int kQfV = 4;
+template <int T> constexpr int qf_v() { return T <= 8 ? kQfV : 2; }
+
+template <typename VT>
+static int launch_mt_qf(const MtLay& lay, const double2* fac, int64_t G, VT* v, int64_t vs, int64_t B, double* partial,
+                        int nblk, hipStream_t st) {
+  const int64_t nv = B / G;
+  if (lay.R == lay.T)
+    return no_kernel(dispatch_range<1, FGP_MT_MAX_TASKS>(lay.T, [&](auto tc) {
+      constexpr int T = decltype(tc)::value, V = qf_v<T>();
+      const int64_t blocks = G * ((nv + V - 1) / V) * nblk;
+      k_mt_qf_reg<VT, T, V><<<(unsigned)blocks, kWG, 0, st>>>(fac, G, lay, v, vs, B, partial, nblk);
+      return check_launch("k_mt_qf_reg");
+    }), "fgp_mt_quadform", lay.T);
+  const int64_t blocks = G * ((nv + kQfV - 1) / kQfV) * nblk;
+  k_mt_qf_gen<VT, kQfV><<<(unsigned)blocks, kWG, 0, st>>>(fac, G, lay, v, vs, B, partial, nblk);
+  return check_launch("k_mt_qf_gen");
+}
+
 // Entries of A = Lambda^-1 on the coupling pattern (Takahashi's recurrence Z = D^-1 L^-1 + (I - L^H) Z,
 // evaluated on the pattern only, which is closed under it): rows (k, q) from the last task back,
 //   Z[(k,q),(m, q mod q_m)] = - sum_{l > k} u_kl[q] Z[(l, q mod q_l), (m, q mod q_m)]     (m > k)
@@ -1074,6 +1240,32 @@ int fgp_mt_solve(const fgp_mt_layout* layout, const void* factor, int64_t G, con
       static_cast<const double2*>(factor), G, lay, static_cast<const double2*>(v), v_row_stride, B,
       static_cast<double2*>(out));
   return check_launch("k_mt_solve");
+}
+
+int fgp_mt_quadform(const fgp_mt_layout* layout, const void* factor, int64_t G, void* v, int64_t v_row_stride,
+                    int64_t B, int v_is_real, double* partial, double* out, void* stream) {
+  if (!layout) return set_error(kErrInvalid, "fgp_mt_quadform: null layout");
+  if (layout->T < 1 || layout->T > FGP_MT_MAX_TASKS)
+    return set_error(kErrInvalid, "fgp_mt_quadform: layout T = %d outside [1, %d]", layout->T, FGP_MT_MAX_TASKS);
+  MtLay lay;
+  int rc = make_layout(layout, &lay);
+  if (rc != kOk) return rc;
+  if (G < 1 || B < 0 || B % G)
+    return set_error(kErrInvalid, "fgp_mt_quadform: G = %lld, B = %lld (B a multiple of G >= 1)", (long long)G, (long long)B);
+  if (v_is_real != 0 && v_is_real != 1) return set_error(kErrInvalid, "fgp_mt_quadform: v_is_real = %d", v_is_real);
+  if (B == 0) return kOk;
+  if (!factor || !v || !partial || !out) return set_error(kErrInvalid, "fgp_mt_quadform: null pointer");
+  if (v_row_stride < (int64_t)lay.R * lay.nmin) return set_error(kErrInvalid, "fgp_mt_quadform: v_row_stride < R * nmin");
+  const int64_t nblk = (lay.nmin + kWG - 1) / kWG;
+  if (B > (((int64_t)1 << 31) - 1) / nblk)
+    return set_error(kErrUnsupported, "fgp_mt_quadform: B * ceil(nmin / %d) partials >= 2^31", kWG);
+  hipStream_t st = (hipStream_t)stream;
+  const double2* fac = static_cast<const double2*>(factor);
+  rc = v_is_real ? launch_mt_qf(lay, fac, G, static_cast<double*>(v), v_row_stride, B, partial, (int)nblk, st)
+                 : launch_mt_qf(lay, fac, G, static_cast<double2*>(v), v_row_stride, B, partial, (int)nblk, st);
+  if (rc != kOk) return rc;
+  k_mt_qf_sum<<<(unsigned)B, kWG, 0, st>>>(partial, nblk, out);
+  return check_launch("k_mt_qf_sum");
 }
 
 int fgp_mt_selinv(const fgp_mt_layout* layout, const void* factor, int64_t G, void* zinv, void* stream) {

@@ -949,8 +949,65 @@ class MultiTaskFastGP(AbstractFastGP):
             all(int(v) >= c for v, c in zip(nt.tolist(), self._ns)), msg
         return [int(v) for v in nt.tolist()]
 
+    def _post_var_qf_bytes(self, ns):
+        """Bytes per (requested task, test point) of a _post_var_qf chunk: the float64 kernel rows and the per-task
+        blocks they are concatenated from, the packed vectors, the largest task's transform and a complex128 scratch of
+        its size."""
+        G = self._factor(ns)[3]
+        vbytes = 8 if self._FAMILY == ops.NET else 16
+        active = sum(v for v in ns if v > 0)
+        return G * (16 * sum(ns) + vbytes * active + (vbytes + 16) * max(ns))
+
+    def _post_var_qf(self, x, tasks, ns, work_bytes=ops.MT_POST_VAR_QF_BYTES):
+        """k^T K^-1 k of every (requested task, test point) -> [*G, T', N] by the transform-domain quadratic form: the
+        per-task transforms are unitary, so it is Re(k~^H Lambda^-1 k~) = sum_classes sum_rows |w|^2 / D with w = L^-1 k~
+        and L D L^H the cached factor (fgp_mt_quadform) -- no inverse transforms, no back substitution, no solution
+        array, no t * kmat product.  In chunks of Tc requested tasks x C test points: the chunk's kernel rows, one
+        forward transform per (point, requested task, task) copied into the packed sorted-task vectors [Tc C G, R nmin]
+        (what _Layout.pack does for the active tasks; a task with n = 0 contributes nothing), the form.  A chunk's
+        arrays -- the rows and their per-task blocks, the packed vectors, the largest task's transform and its scratch
+        -- stay within work_bytes (one task and one point are always allowed); the packed vectors are allocated once.
+        The requested tasks are split before the points: a kernel block K_{t,l}(x, .) costs the host the same
+        whatever its number of points (measured: ~0.12 ms), so T' chunks of all points make the T' T block calls of
+        the unchunked rows, while every chunk over the points makes them again."""
+        lo, fac, _, G, gshape = self._factor(ns)
+        gshape = tuple(gshape)
+        Tq, Nt, nb = len(tasks), x.shape[0], len(gshape)
+        vdt = torch.float64 if self._FAMILY == ops.NET else torch.complex128
+        rn = lo.R * lo.nmin
+        per = self._post_var_qf_bytes(ns)
+        C = max(1, min(Nt, work_bytes // per))
+        Tc = max(1, min(Tq, work_bytes // (per * Nt))) if C == Nt else 1
+        buf = None
+        out = torch.empty(gshape + (Tq, Nt), dtype=torch.float64, device=self.device)
+        toff = np.concatenate([[0], np.cumsum(ns)])
+        perm = [nb, nb + 1] + list(range(nb)) + [nb + 2]          # [*G, Tc, c, n] -> [Tc, c, *G, n]
+        for t0 in range(0, Tq, Tc):
+            tg = tasks[t0:t0 + Tc]
+            for c0 in range(0, Nt, C):
+                c = min(C, Nt - c0)
+                kmat = self._kmat_rows(x[c0:c0 + c], tg, ns)      # [*G (broadcastable), Tc, c, sum n]
+                assert kmat.ndim <= nb + 3
+                kmat = kmat.reshape((1,) * (nb + 3 - kmat.ndim) + kmat.shape)
+                if buf is None:                                   # (after the first rows: their temporaries are gone)
+                    buf = torch.empty((Tc * C * G, rn), dtype=vdt, device=self.device)
+                v = buf[:len(tg) * c * G]
+                vview = v.view((len(tg), c) + gshape + (rn,))
+                so = 0
+                for o in lo.active:
+                    seg = self.ft(kmat[..., int(toff[o]):int(toff[o + 1])])
+                    vview[..., so:so + ns[o]].copy_(seg.expand(gshape + seg.shape[-3:]).permute(perm))
+                    so += ns[o]
+                    del seg
+                del kmat
+                q = ops.mt_quadform(lo.lay, fac, v).view((len(tg), c) + gshape)
+                out[..., t0:t0 + len(tg), c0:c0 + c] = q.permute(list(range(2, 2 + nb)) + [0, 1])
+        return out
+
     def post_var(self, x, task=None, n=None, eval=True):
-        """abstract_fast_gp.py:41-46 + abstract_gp.py:381-416."""
+        """abstract_fast_gp.py:41-46 + abstract_gp.py:381-416.  Without an autograd graph, at sum n >= 2^13, nmin >=
+        256 and while a requested task's test points fit one 2^28-byte chunk (ops.mt_post_var_qf; FGP_MT_POST_VAR_QF=1 /
+        0 forces either route): the quadratic form of _post_var_qf, else the reference's kernel rows and transform solve."""
         ns = self._check_n(n, "require n are all power of two greater than or equal to self.n")
         assert x.ndim == 2 and x.size(1) == self.d, "x must a torch.Tensor with shape (-1,d)"
         with (torch.no_grad() if eval else torch.enable_grad() if torch.is_grad_enabled() else torch.no_grad()):
@@ -961,12 +1018,17 @@ class MultiTaskFastGP(AbstractFastGP):
                     for t in tasks]
             bs = torch.broadcast_shapes(*[k.shape[:-2] for k in knew])
             kmat_new = torch.cat([k.expand(bs + k.shape[-2:]) for k in knew], -2)
-            kmat = self._kmat_rows(x, tasks, ns)
-            nb = kmat.ndim - 3
-            kperm = kmat.permute([nb, nb + 1] + list(range(nb)) + [kmat.ndim - 1])
-            tperm = self.gram_matrix_solve(kperm, ns)
-            t = tperm.permute(list(range(2, 2 + nb)) + [0, 1, tperm.ndim - 1])
-            diag = kmat_new - (t * kmat).sum(-1)
+            active = [v for v in ns if v > 0]
+            if not self._gradmode() and x.shape[0] > 0 and active and ops.mt_post_var_qf(
+                    active, lambda: x.shape[0] * self._post_var_qf_bytes(ns) <= ops.MT_POST_VAR_QF_BYTES):
+                diag = kmat_new - self._post_var_qf(x, tasks, ns)
+            else:
+                kmat = self._kmat_rows(x, tasks, ns)
+                nb = kmat.ndim - 3
+                kperm = kmat.permute([nb, nb + 1] + list(range(nb)) + [kmat.ndim - 1])
+                tperm = self.gram_matrix_solve(kperm, ns)
+                t = tperm.permute(list(range(2, 2 + nb)) + [0, 1, tperm.ndim - 1])
+                diag = kmat_new - (t * kmat).sum(-1)
             diag = torch.where(diag < 0, torch.zeros_like(diag), diag)
         return diag[..., 0, :] if inttask else diag
 

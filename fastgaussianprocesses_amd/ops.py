@@ -627,6 +627,27 @@ def wide_post_var_qf():
     return os.environ.get("FGP_WIDE_POST_VAR_QF", "1")[:1] != "0"
 
 
+MT_POST_VAR_QF_NSUM = 1 << 13      # default rule of the multitask form: sum_l n_l >= this ...
+MT_POST_VAR_QF_NMIN = 256          # ... and nmin >= this (fewer classes: the thread-per-class kernel has too few)
+MT_POST_VAR_QF_BYTES = 1 << 28     # scratch of a chunk of the form (multitask.py _post_var_qf's work_bytes)
+
+
+def mt_post_var_qf(ns_active, one_chunk=None):
+    """The route of a multitask post_var over the active tasks' n: the transform-domain quadratic form (fgp_mt_quadform)
+    or the kernel rows and the transform solve.  FGP_MT_POST_VAR_QF=1: the form at any size (tests, and calls whose
+    rows-and-solve arrays do not fit: the form's scratch is bounded); =0: rows-and-solve everywhere (A/B runs); default:
+    the form when sum n >= 2^13, nmin >= 256 and one_chunk() -- all test points of a requested task fit one chunk of
+    MT_POST_VAR_QF_BYTES.  (A chunk over the test points repeats the host cost of the T' T kernel blocks, and a call
+    that needs one was measured slower than rows-and-solve at d = 3)  one_chunk: a callable,
+    asked only when the sizes pass; None: not consulted."""
+    env = os.environ.get("FGP_MT_POST_VAR_QF", "")[:1]
+    if env in ("0", "1"):
+        return env == "1"
+    if not (sum(ns_active) >= MT_POST_VAR_QF_NSUM and min(ns_active) >= MT_POST_VAR_QF_NMIN):
+        return False
+    return one_chunk is None or bool(one_chunk())
+
+
 def wide_post_var_quadform(family, xt, z, hyp, wa, alphas=None, tbits=0):
     """q[p, t] = sum_k wa_p[k] |ft(K_p(xt_p[t], z_p))_k|^2 -> [P, N] (fgp_wide_post_var_qf), 9 <= d <= 64, n = 2^13..2^24.
 
@@ -762,6 +783,8 @@ def wide_mt_parts(spec, x, z, zip_pairs=False):
     assert d == spec.d and z.shape[1] == d and (not zip_pairs or Nx == M)
     E = Nx if zip_pairs else Nx * M
     out = torch.empty((spec.P, d, E), dtype=torch.float64, device=x.device)
+    if E == 0:                                              # (an empty task's points: nothing to launch)
+        return out
     for p0 in range(0, spec.P, N.WIDE_MT_MAX_P):
         p1 = min(spec.P, p0 + N.WIDE_MT_MAX_P)
         b = spec.block(p0, p1)
@@ -881,6 +904,27 @@ def mt_solve(lay, fac, v):
     out = torch.empty((B, v.shape[1]), dtype=torch.complex128, device=v.device)
     N.call("fgp_mt_solve", N.byref_layout(lay), N.ptr(fac), fac.shape[0], N.ptr(v), v.stride(0) if B > 1 else v.shape[1],
            B, N.ptr(out), _stream(v))
+    return out
+
+
+def mt_quadform(lay, fac, v, out=None):
+    """q[b] = v[b]^H Lambda_{b mod G}^-1 v[b] = sum_j sum_r |w_rj|^2 / D_rj, w = L^-1 v (fgp_mt_quadform) -> [B] float64.
+    v [B, R nmin]: complex128 (lattices), or float64 (nets: the real form).  Unless the tasks' n are all equal the
+    substitution runs in place: a v that the kernel can take as it is (unit inner stride, rows not overlapping) IS
+    OVERWRITTEN; any other is copied first."""
+    require_device(v, "mt_quadform")
+    real = not v.is_complex()
+    v = resolved(v.to(torch.float64 if real else torch.complex128))
+    v = v if v.stride(-1) == 1 and (v.shape[0] <= 1 or v.stride(0) >= v.shape[1]) else v.contiguous()
+    B = v.shape[0]
+    nmin = int(lay.n[lay.T - 1])
+    assert v.dim() == 2 and v.shape[1] == sum(int(lay.n[k]) for k in range(lay.T)), "mt_quadform: v must be [B, R nmin]"
+    assert fac.dim() == 2 and B % fac.shape[0] == 0, "mt_quadform: B must be a multiple of the factor's problems"
+    partial = torch.empty((B, (nmin + 255) // 256), dtype=torch.float64, device=v.device)
+    out = torch.empty(B, dtype=torch.float64, device=v.device) if out is None else out
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == B
+    N.call("fgp_mt_quadform", N.byref_layout(lay), N.ptr(fac), fac.shape[0], N.ptr(v),
+           v.stride(0) if B > 1 else v.shape[1], B, int(real), N.ptr(partial), N.ptr(out), _stream(v))
     return out
 
 

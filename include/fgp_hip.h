@@ -709,6 +709,28 @@ int fgp_mt_factor(const fgp_mt_layout* layout, const void* lams, int64_t G, void
 int fgp_mt_solve(const fgp_mt_layout* layout, const void* factor, int64_t G, const void* v, int64_t v_row_stride,
                  int64_t B, void* out, void* stream);
 
+/* Addition to ABI 20 -- the quadratic form of the posterior variance of multitask / derivative-informed GPs
+ * (abstract_gp.py:407-413's k^T K^-1 k in the transform domain: the per-task transforms are unitary, so it is
+ * Re(k~^H Lambda^-1 k~) and, with Lambda = L D L^H of fgp_mt_factor, a weighted sum of squares):
+ *   out[b] = sum_j sum_r |w_{b,r,j}|^2 / D_{g,r,j},   w_b = L_g^-1 v[b],   g = b mod G,
+ * for B vectors v [B][R nmin] (row stride v_row_stride >= R nmin elements), B a multiple of G: fgp_mt_solve's factor,
+ * packed layout, row order and vector-to-problem mapping.  v_is_real = 0: v complex128 (lattices); v_is_real = 1: v
+ * float64 (nets) against the real parts of the couplings (the factor of a real symmetric problem; factor stays
+ * complex128 [G][L]).  The forward substitution is fgp_mt_solve's, update for update; the pivot enters as 1 / D, a
+ * non-positive one like any other (fgp_mt_factor's *info flags it).  No D scaling of the vector, no back substitution,
+ * no solution array.
+ * Equal n (R = T): v is only read.  ANY OTHER LAYOUT: the substitution runs in place and v IS OVERWRITTEN by w.
+ * Sums, all in a fixed order and without atomics: ascending rows within a class; the classes of a workgroup (256) by
+ * thread, wave butterfly, waves in order into partial [B][ceil(nmin / 256)] (device float64 scratch); the partials of a
+ * vector by a thread over every 256th in ascending order and the same tree.  out[b] (device [B]) has the same bits
+ * whatever B, G's other problems or the other vectors of the call are.
+ * Validated before any HIP call (also without a device): a null layout, T outside 1 .. FGP_MT_MAX_TASKS, an n that is
+ * not a power of two or not descending, G < 1, B < 0, B not a multiple of G, v_is_real outside {0, 1}, a null pointer,
+ * v_row_stride < R nmin: FGP_ERR_INVALID with the argument named (B = 0 returns FGP_OK); R > FGP_MT_MAX_ROWS or
+ * B ceil(nmin / 256) >= 2^31: FGP_ERR_UNSUPPORTED.  (`extern` as the additions above.) */
+extern int fgp_mt_quadform(const fgp_mt_layout* layout, const void* factor, int64_t G, void* v, int64_t v_row_stride,
+                           int64_t B, int v_is_real, double* partial, double* out, void* stream);
+
 /* Entries of A = Lambda^-1 on the packed coupling pattern (zinv [G][L]): the entries of the reference's
  * dense inverse `inv` (util.py:336) that the MLL gradient and post_cubature_var / cov
  * (abstract_fast_gp.py:82-154, inv[mvec, mvec, 0]) read. */
