@@ -248,6 +248,8 @@ _SIGNATURES = {
     "fgp_wide_mt_fit_run": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
     # addition to ABI 20: the multitask posterior variance's quadratic form
     "fgp_mt_quadform": [_P_MT, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp],
+    # addition to ABI 20: test hook, no HIP call -- where fgp_mt_fit_run keeps its intermediates in `work`
+    "fgp_mt_fit_work_layout": [_P_MTFIT, _c_pl],
 }
 
 

@@ -1096,7 +1096,7 @@ static int make_layout(const fgp_mt_layout* in, MtLay* lay) {
 
 static size_t mtg_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-static int to_mtfit(const fgp_mt_fit_desc* d, MtFit* m, int64_t* work_bytes) {
+static int to_mtfit(const fgp_mt_fit_desc* d, MtFit* m, int64_t* work_bytes, int64_t* work_offsets = nullptr) {
   if (!d) return set_error(kErrInvalid, "fgp_mt_fit: null desc");
   *m = MtFit{};
   int rc = make_layout(&d->layout, &m->lay);
@@ -1175,6 +1175,10 @@ static int to_mtfit(const fgp_mt_fit_desc* d, MtFit* m, int64_t* work_bytes) {
   const size_t o_sums = off; off += mtg_align(8 * (size_t)(G * (kMtgQ + m->P)));
   const size_t o_info = off; off += 256;
   if (work_bytes) *work_bytes = (int64_t)off;
+  if (work_offsets) {
+    const size_t o[10] = {o_lams, o_fac, o_zinv, o_glp, o_z, o_ld, o_dkt, o_part, o_sums, o_info};
+    for (int q = 0; q < 10; ++q) work_offsets[q] = (int64_t)o[q];
+  }
   char* w = static_cast<char*>(d->work);
   if (w) {
     m->lams = reinterpret_cast<double2*>(w + o_lams);
@@ -1314,6 +1318,12 @@ int fgp_mt_fit_work(const fgp_mt_fit_desc* desc, int64_t* bytes) {
   MtFit m;
   if (!bytes) return set_error(kErrInvalid, "fgp_mt_fit_work: null bytes");
   return to_mtfit(desc, &m, bytes);
+}
+
+int fgp_mt_fit_work_layout(const fgp_mt_fit_desc* desc, int64_t offsets[10]) {
+  MtFit m;
+  if (!offsets) return set_error(kErrInvalid, "fgp_mt_fit_work_layout: null offsets");
+  return to_mtfit(desc, &m, nullptr, offsets);
 }
 
 int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {

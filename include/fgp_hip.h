@@ -827,6 +827,15 @@ typedef struct fgp_mt_fit_desc {
 
 int fgp_mt_fit_nparams(const fgp_mt_fit_desc* desc, int* n_params);
 int fgp_mt_fit_work(const fgp_mt_fit_desc* desc, int64_t* bytes);
+/* Addition to ABI 20 -- test hook (no reference counterpart), read-only: the byte offsets in `work` of the arrays an
+ * iteration leaves there, offsets[0..9] = { lams, fac, zinv, glp [G][L] complex128; z [G][B][R nmin] complex128 (problem
+ * g's B solutions together); logdet [G][nmin]; dkt [G][L] (dL/dK_task per entry); part [G][nblk][4 + FGP_MAX_D] (the
+ * contraction's workgroup partials); sums [G][4 + FGP_MAX_D + T (T + 1) / 2] (norm, logdet, dnoise / noise, draw_scale,
+ * draw_l[d], then dL/dK_task per sorted pair); info (int) }, each a multiple of 256, ascending, the last + 256 =
+ * fgp_mt_fit_work's bytes.  fac and zinv are stored by the thread-per-class kernel only (fgp_set_mt_class_kernel: the
+ * wave-per-class kernel keeps them in LDS; no later stage reads them).  The desc is validated as fgp_mt_fit_work
+ * validates it (no pointer of it is followed, no HIP call is made); NULL offsets returns FGP_ERR_INVALID. */
+extern int fgp_mt_fit_work_layout(const fgp_mt_fit_desc* desc, int64_t offsets[10]);
 /* iterations iter0 .. iter0 + iters - 1 (history rows); with final_no_update the last one evaluates only */
 int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
 

@@ -19,7 +19,8 @@ torch.set_default_dtype(torch.float64)
 def header_functions():
     src = open(os.path.join(ROOT, "include", "fgp_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\*?\s+\*?(fgp_\w+)\s*\(", src, flags=re.M)))
+    # (the later additions are declared `extern int fgp_name(`, two of them with the name in parentheses)
+    return sorted(set(re.findall(r"^\s*(?:extern\s+)?(?:const\s+)?\w+\*?\s+\*?\(?(fgp_\w+)\)?\s*\(", src, flags=re.M)))
 
 
 def test_library_exports_every_declared_symbol():
