@@ -250,6 +250,11 @@ _SIGNATURES = {
     "fgp_mt_quadform": [_P_MT, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_int, _c_vp, _c_vp, _c_vp],
     # addition to ABI 20: test hook, no HIP call -- where fgp_mt_fit_run keeps its intermediates in `work`
     "fgp_mt_fit_work_layout": [_P_MTFIT, _c_pl],
+    # additions to ABI 20: test hooks -- the wide fit loops' work layouts, and one stage of an iteration at a time
+    "fgp_wide_fit_work_layout": [_P_WIDEFIT, _c_pl],
+    "fgp_wide_fit_stage": [_P_WIDEFIT, _c_int, _c_int, _c_int, _c_vp],
+    "fgp_wide_mt_fit_work_layout": [_P_WIDEMTFIT, _c_pl],
+    "fgp_wide_mt_fit_stage": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
 }
 
 

@@ -449,33 +449,64 @@ static int wide_fit_plan(const char* fn, const fgp_wide_fit_desc* a, WideFitPlan
   return kOk;
 }
 
-// The two GCV / CV passes of one iteration over lambda (B) and Y.
-template <int FAM, bool CV>
-static int wide_fit_loss_terms_t(dim3 grid, double* B, const double* ysq, const double* raw_noise, int64_t n,
-                                 double sqrtn, double w, int nbe, double* pe, hipStream_t st) {
-  k_wide_fit_loss_sums<FAM, CV><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
-  const int rc = check_launch("k_wide_fit_loss_sums");
-  if (rc != kOk) return rc;
-  k_wide_fit_loss_grad<FAM, CV><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+// The two GCV / CV passes of one iteration over lambda (B) and Y, one launch each.
+static int wide_fit_loss_sums(bool lat, bool cv, dim3 grid, const double* B, const double* ysq, const double* raw_noise,
+                              int64_t n, double sqrtn, int nbe, double* pe, hipStream_t st) {
+  if (lat) {
+    if (cv) k_wide_fit_loss_sums<0, true><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
+    else k_wide_fit_loss_sums<0, false><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
+  } else {
+    if (cv) k_wide_fit_loss_sums<1, true><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
+    else k_wide_fit_loss_sums<1, false><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, nbe, pe);
+  }
+  return check_launch("k_wide_fit_loss_sums");
+}
+
+static int wide_fit_loss_grad(bool lat, bool cv, dim3 grid, double* B, const double* ysq, const double* raw_noise,
+                              int64_t n, double sqrtn, double w, int nbe, const double* pe, hipStream_t st) {
+  if (lat) {
+    if (cv) k_wide_fit_loss_grad<0, true><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+    else k_wide_fit_loss_grad<0, false><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+  } else {
+    if (cv) k_wide_fit_loss_grad<1, true><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+    else k_wide_fit_loss_grad<1, false><<<grid, kWG, 0, st>>>(B, ysq, raw_noise, n, sqrtn, w, nbe, pe);
+  }
   return check_launch("k_wide_fit_loss_grad");
 }
 
-static int wide_fit_loss_terms(bool lat, bool cv, dim3 grid, double* B, const double* ysq, const double* raw_noise,
-                               int64_t n, double sqrtn, double w, int nbe, double* pe, hipStream_t st) {
-  if (lat) return cv ? wide_fit_loss_terms_t<0, true>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st)
-                     : wide_fit_loss_terms_t<0, false>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st);
-  return cv ? wide_fit_loss_terms_t<1, true>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st)
-            : wide_fit_loss_terms_t<1, false>(grid, B, ysq, raw_noise, n, sqrtn, w, nbe, pe, st);
-}
+// One iteration as stages, in the order wide_fit_run enqueues them.  fgp_wide_fit_stage (a test hook) enqueues one of
+// them; wide_fit_run is the loop over the same function, so the run and the staged sequence are one piece of code.
+enum WideFitStage {
+  kWfsPrologue = 0,   // k_wide_fit_step in mode 0; the stage's mode is its init flag
+  kWfsK1,             // fgp_wide_k1 (per problem when every problem has its own parts)
+  kWfsForward,        // lambda = ft(k1)
+  kWfsTerms,          // k_wide_fit_eig; GCV / CV: k_wide_fit_loss_sums
+  kWfsTerms2,         // GCV / CV only: k_wide_fit_loss_grad
+  kWfsAdjoint,        // u = the adjoint transform of g~
+  kWfsK1Bwd,          // fgp_wide_k1_bwd
+  kWfsStep,           // k_wide_fit_step in mode 1 or 2
+  kWfsCount
+};
 
-static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int iter0, int iters, int final_no_update,
-                        hipStream_t st) {
-  const int G = a->G, d = a->d, m = a->log2n;
-  const int64_t n = p.n;
+// what every stage needs of the desc and the plan, formed once per run
+struct WideFitCtx {
+  const fgp_wide_fit_desc* a;
+  const WideFitPlan* p;
+  WideFitStep s;
+  WideFitLoss x;
+  double *nat_scale, *nat_ls, *dscale, *dls, *A, *B, *W, *pe, *pb;
+  const double* raw_noise;
+  double sqrtn;
+};
+
+static WideFitCtx wide_fit_ctx(const fgp_wide_fit_desc* a, const WideFitPlan& p) {
+  WideFitCtx c{};
+  c.a = a, c.p = &p;
+  const int G = a->G, d = a->d;
   double* work = static_cast<double*>(a->work);
-  double *nat_scale = work + p.o_scale, *nat_ls = work + p.o_ls, *dscale = work + p.o_dscale, *dls = work + p.o_dls;
-  double *A = work + p.o_a, *B = work + p.o_b, *W = work + p.o_w, *pe = work + p.o_pe, *pb = work + p.o_pb;
-  WideFitStep s{};
+  c.nat_scale = work + p.o_scale, c.nat_ls = work + p.o_ls, c.dscale = work + p.o_dscale, c.dls = work + p.o_dls;
+  c.A = work + p.o_a, c.B = work + p.o_b, c.W = work + p.o_w, c.pe = work + p.o_pe, c.pb = work + p.o_pb;
+  WideFitStep& s = c.s;
   s.f.n_params = G * (2 + a->dl);
   s.f.raw = a->raw;
   s.f.prev = a->rprop_prev;
@@ -488,60 +519,107 @@ static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int it
   s.f.eta_minus = a->eta_minus, s.f.eta_plus = a->eta_plus, s.f.step_min = a->step_min, s.f.step_max = a->step_max;
   s.G = G, s.d = d, s.dl = a->dl, s.nbe = p.nbe;
   s.w = a->logdet_weight, s.lr = a->lr;
-  if (a->loss_metric != FGP_LOSS_MLL) pe = work + p.o_pl;
-  s.pe = pe, s.dscale = dscale, s.dls = dls, s.nat_scale = nat_scale, s.nat_ls = nat_ls;
-  const double* raw_noise = a->raw + (int64_t)G * (1 + a->dl);
-  const double sqrtn = std::sqrt((double)n);
-  const int loss = a->loss_metric;
-  const WideFitLoss x{(double)n, a->cv_weight};
-  auto step = [&](int iter, int mode, int init) {
-    if (loss == FGP_LOSS_MLL) k_wide_fit_step<FGP_LOSS_MLL><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
-    else if (loss == FGP_LOSS_GCV) k_wide_fit_step<FGP_LOSS_GCV><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
-    else k_wide_fit_step<FGP_LOSS_CV><<<G, kWG, 0, st>>>(s, iter, mode, init, x);
-    return check_launch("k_wide_fit_step");
-  };
-  int rc = step(0, 0, iter0 == 0 && a->lr > 0.0);
+  if (a->loss_metric != FGP_LOSS_MLL) c.pe = work + p.o_pl;
+  s.pe = c.pe, s.dscale = c.dscale, s.dls = c.dls, s.nat_scale = c.nat_scale, s.nat_ls = c.nat_ls;
+  c.raw_noise = a->raw + (int64_t)G * (1 + a->dl);
+  c.sqrtn = std::sqrt((double)p.n);
+  c.x = WideFitLoss{(double)p.n, a->cv_weight};
+  return c;
+}
+
+static int wide_fit_step_launch(const WideFitCtx& c, int iter, int mode, int init, hipStream_t st) {
+  const int loss = c.a->loss_metric, G = c.a->G;
+  if (loss == FGP_LOSS_MLL) k_wide_fit_step<FGP_LOSS_MLL><<<G, kWG, 0, st>>>(c.s, iter, mode, init, c.x);
+  else if (loss == FGP_LOSS_GCV) k_wide_fit_step<FGP_LOSS_GCV><<<G, kWG, 0, st>>>(c.s, iter, mode, init, c.x);
+  else k_wide_fit_step<FGP_LOSS_CV><<<G, kWG, 0, st>>>(c.s, iter, mode, init, c.x);
+  return check_launch("k_wide_fit_step");
+}
+
+// Stage `stage` of iteration `iter` (the history row the step writes).  mode: the prologue's init flag, the step's mode
+// (1 or 2), otherwise unused.  The caller has validated stage and mode.
+static int wide_fit_stage(const WideFitCtx& c, int iter, int stage, int mode, hipStream_t st) {
+  const fgp_wide_fit_desc* a = c.a;
+  const WideFitPlan& p = *c.p;
+  const int G = a->G, d = a->d, m = a->log2n, loss = a->loss_metric;
+  const int64_t n = p.n;
+  const dim3 grid((unsigned)p.nbe, (unsigned)G);
+  int rc = kOk;
+  switch (stage) {
+    case kWfsPrologue:
+      return wide_fit_step_launch(c, 0, 0, mode, st);
+    case kWfsK1:
+      // per problem when every problem has its own parts: fgp_wide_k1 takes ONE parts array
+      if (a->parts_stride == 0) return fgp_wide_k1(a->parts, n, d, c.nat_scale, c.nat_ls, G, c.A, st);
+      for (int g = 0; g < G && rc == kOk; ++g)
+        rc = fgp_wide_k1(a->parts + g * a->parts_stride, n, d, c.nat_scale + g, c.nat_ls + (int64_t)g * d, 1, c.A + g * n,
+                         st);
+      return rc;
+    case kWfsForward:
+      // lambda = ft(k1), stable (AbstractFastGP.ft)
+      if (!p.lat) return fgp_fwht(c.A, n, c.B, G, m, 1, st);
+      if (p.r2c) return fgp_fftbr_real(c.A, n, c.B, c.W, G, m, st);
+      return fgp_fftbr(c.A, n, 1, c.B, G, m, 1, st);
+    case kWfsTerms:
+      if (loss == FGP_LOSS_MLL) {
+        if (p.lat)
+          k_wide_fit_eig<0><<<grid, kWG, 0, st>>>(c.B, a->ysq, c.raw_noise, n, c.sqrtn, a->logdet_weight, p.nbe, c.pe);
+        else
+          k_wide_fit_eig<1><<<grid, kWG, 0, st>>>(c.B, a->ysq, c.raw_noise, n, c.sqrtn, a->logdet_weight, p.nbe, c.pe);
+        return check_launch("k_wide_fit_eig");
+      }
+      return wide_fit_loss_sums(p.lat, loss == FGP_LOSS_CV, grid, c.B, a->ysq, c.raw_noise, n, c.sqrtn, p.nbe, c.pe, st);
+    case kWfsTerms2:
+      return wide_fit_loss_grad(p.lat, loss == FGP_LOSS_CV, grid, c.B, a->ysq, c.raw_noise, n, c.sqrtn, a->cv_weight,
+                                p.nbe, c.pe, st);
+    case kWfsAdjoint:
+      // u = dL/dk1: the adjoint transform of g~ (lattice: the real part)
+      if (!p.lat) return fgp_fwht(c.B, n, c.A, G, m, 1, st);
+      if (p.r2c) return fgp_ifftbr_real(c.B, n, nullptr, 0, c.A, n, c.W, G, m, st);
+      return fgp_ifftbr(c.B, n, c.A, 1, c.W, G, m, 1, st);
+    case kWfsK1Bwd:
+      if (a->parts_stride == 0)
+        return fgp_wide_k1_bwd(a->parts, n, d, c.nat_scale, c.nat_ls, G, c.A, c.dscale, c.dls, c.pb, st);
+      for (int g = 0; g < G && rc == kOk; ++g)
+        rc = fgp_wide_k1_bwd(a->parts + g * a->parts_stride, n, d, c.nat_scale + g, c.nat_ls + (int64_t)g * d, 1,
+                             c.A + g * n, c.dscale + g, c.dls + (int64_t)g * d, c.pb, st);
+      return rc;
+    default:
+      return wide_fit_step_launch(c, iter, mode, 0, st);
+  }
+}
+
+static int wide_fit_run(const fgp_wide_fit_desc* a, const WideFitPlan& p, int iter0, int iters, int final_no_update,
+                        hipStream_t st) {
+  const WideFitCtx c = wide_fit_ctx(a, p);
+  int rc = wide_fit_stage(c, 0, kWfsPrologue, iter0 == 0 && a->lr > 0.0, st);
   for (int it = 0; it < iters && rc == kOk; ++it) {
-    // k1 (per problem when every problem has its own parts: fgp_wide_k1 takes ONE parts array)
-    if (a->parts_stride == 0) {
-      rc = fgp_wide_k1(a->parts, n, d, nat_scale, nat_ls, G, A, st);
-    } else {
-      for (int g = 0; g < G && rc == kOk; ++g)
-        rc = fgp_wide_k1(a->parts + g * a->parts_stride, n, d, nat_scale + g, nat_ls + (int64_t)g * d, 1, A + g * n, st);
-    }
-    if (rc != kOk) break;
-    // lambda = ft(k1), stable (AbstractFastGP.ft)
-    if (!p.lat) rc = fgp_fwht(A, n, B, G, m, 1, st);
-    else if (p.r2c) rc = fgp_fftbr_real(A, n, B, W, G, m, st);
-    else rc = fgp_fftbr(A, n, 1, B, G, m, 1, st);
-    if (rc != kOk) break;
-    const dim3 grid((unsigned)p.nbe, (unsigned)G);
-    if (loss == FGP_LOSS_MLL) {
-      if (p.lat) k_wide_fit_eig<0><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
-      else k_wide_fit_eig<1><<<grid, kWG, 0, st>>>(B, a->ysq, raw_noise, n, sqrtn, a->logdet_weight, p.nbe, pe);
-      rc = check_launch("k_wide_fit_eig");
-    } else {
-      rc = wide_fit_loss_terms(p.lat, loss == FGP_LOSS_CV, grid, B, a->ysq, raw_noise, n, sqrtn, a->cv_weight, p.nbe, pe,
-                               st);
-    }
-    if (rc != kOk) break;
-    // u = dL/dk1: the adjoint transform of g~ (lattice: the real part)
-    if (!p.lat) rc = fgp_fwht(B, n, A, G, m, 1, st);
-    else if (p.r2c) rc = fgp_ifftbr_real(B, n, nullptr, 0, A, n, W, G, m, st);
-    else rc = fgp_ifftbr(B, n, A, 1, W, G, m, 1, st);
-    if (rc != kOk) break;
-    if (a->parts_stride == 0) {
-      rc = fgp_wide_k1_bwd(a->parts, n, d, nat_scale, nat_ls, G, A, dscale, dls, pb, st);
-    } else {
-      for (int g = 0; g < G && rc == kOk; ++g)
-        rc = fgp_wide_k1_bwd(a->parts + g * a->parts_stride, n, d, nat_scale + g, nat_ls + (int64_t)g * d, 1, A + g * n,
-                             dscale + g, dls + (int64_t)g * d, pb, st);
-    }
-    if (rc != kOk) break;
     const bool last = it + 1 == iters;
-    rc = step(iter0 + it, (last && final_no_update) ? 1 : 2, 0);
+    for (int stage = kWfsK1; stage < kWfsCount && rc == kOk; ++stage) {
+      if (stage == kWfsTerms2 && a->loss_metric == FGP_LOSS_MLL) continue;
+      rc = wide_fit_stage(c, iter0 + it, stage, stage == kWfsStep ? ((last && final_no_update) ? 1 : 2) : 0, st);
+    }
   }
   return rc;
+}
+
+// what fgp_wide_fit_run and fgp_wide_fit_stage validate beyond the plan: the pointers, then (after the caller's own
+// iteration arguments, the order fgp_wide_fit_run has always reported them in) the alignment
+static int wide_fit_check_ptrs(const char* fn, const fgp_wide_fit_desc* desc) {
+  const struct {
+    const void* ptr;
+    const char* name;
+  } ptrs[] = {{desc->parts, "parts"},           {desc->ysq, "ysq"},           {desc->raw, "raw"},
+              {desc->rprop_prev, "rprop_prev"}, {desc->rprop_step, "rprop_step"}, {desc->loss_hist, "loss_hist"},
+              {desc->raw_hist, "raw_hist"},     {desc->grad_out, "grad_out"}, {desc->work, "work"}};
+  for (const auto& q : ptrs)
+    if (!q.ptr) return set_error(kErrInvalid, "%s: null pointer: %s", fn, q.name);
+  return kOk;
+}
+
+static int wide_fit_check_align(const char* fn, const fgp_wide_fit_desc* desc) {
+  if (((uintptr_t)desc->ysq | (uintptr_t)desc->work) & 15)
+    return set_error(kErrInvalid, "%s: ysq and work must be 16-byte aligned", fn);
+  return kOk;
 }
 
 }  // namespace fgp
@@ -563,20 +641,49 @@ int fgp_wide_fit_run(const fgp_wide_fit_desc* desc, int iter0, int iters, int fi
   WideFitPlan p;
   int rc = wide_fit_plan("fgp_wide_fit_run", desc, p);
   if (rc != kOk) return rc;
-  const struct {
-    const void* ptr;
-    const char* name;
-  } ptrs[] = {{desc->parts, "parts"},           {desc->ysq, "ysq"},           {desc->raw, "raw"},
-              {desc->rprop_prev, "rprop_prev"}, {desc->rprop_step, "rprop_step"}, {desc->loss_hist, "loss_hist"},
-              {desc->raw_hist, "raw_hist"},     {desc->grad_out, "grad_out"}, {desc->work, "work"}};
-  for (const auto& q : ptrs)
-    if (!q.ptr) return set_error(kErrInvalid, "fgp_wide_fit_run: null pointer: %s", q.name);
+  rc = wide_fit_check_ptrs("fgp_wide_fit_run", desc);
+  if (rc != kOk) return rc;
   if (iters < 0) return set_error(kErrInvalid, "fgp_wide_fit_run: iters=%d negative", iters);
   if (iter0 < 0) return set_error(kErrInvalid, "fgp_wide_fit_run: iter0=%d negative", iter0);
-  if (((uintptr_t)desc->ysq | (uintptr_t)desc->work) & 15)
-    return set_error(kErrInvalid, "fgp_wide_fit_run: ysq and work must be 16-byte aligned");
+  rc = wide_fit_check_align("fgp_wide_fit_run", desc);
+  if (rc != kOk) return rc;
   if (iters == 0) return kOk;
   return wide_fit_run(desc, p, iter0, iters, final_no_update, (hipStream_t)stream);
+}
+
+int fgp_wide_fit_work_layout(const fgp_wide_fit_desc* desc, int64_t offsets[10]) {
+  WideFitPlan p;
+  int rc = wide_fit_plan("fgp_wide_fit_work_layout", desc, p);
+  if (rc != kOk) return rc;
+  if (!offsets) return set_error(kErrInvalid, "fgp_wide_fit_work_layout: null pointer: offsets");
+  const int64_t o[10] = {p.o_scale, p.o_ls, p.o_dscale, p.o_dls, p.o_a, p.o_b, p.o_w, p.o_pe, p.o_pb, p.o_pl};
+  for (int i = 0; i < 10; ++i) offsets[i] = o[i];
+  return kOk;
+}
+
+int fgp_wide_fit_stage(const fgp_wide_fit_desc* desc, int iter, int stage, int mode, void* stream) {
+  static const char* fn = "fgp_wide_fit_stage";
+  WideFitPlan p;
+  int rc = wide_fit_plan(fn, desc, p);
+  if (rc != kOk) return rc;
+  rc = wide_fit_check_ptrs(fn, desc);
+  if (rc != kOk) return rc;
+  if (iter < 0) return set_error(kErrInvalid, "%s: iter=%d negative", fn, iter);
+  rc = wide_fit_check_align(fn, desc);
+  if (rc != kOk) return rc;
+  if (stage < 0 || stage >= kWfsCount) return set_error(kErrInvalid, "%s: stage=%d outside 0..%d", fn, stage, kWfsCount - 1);
+  if (stage == kWfsTerms2 && desc->loss_metric == FGP_LOSS_MLL)
+    return set_error(kErrInvalid, "%s: stage=%d (the second terms pass) exists under GCV / CV only", fn, stage);
+  if (stage == kWfsPrologue) {
+    if (mode != 0 && mode != 1) return set_error(kErrInvalid, "%s: mode=%d of the prologue is not 0 or 1 (init)", fn, mode);
+    if (mode == 1 && !(desc->lr > 0.0)) return set_error(kErrInvalid, "%s: mode=1 (init) needs lr > 0", fn);
+  } else if (stage == kWfsStep) {
+    if (mode != 1 && mode != 2) return set_error(kErrInvalid, "%s: mode=%d of the step is not 1 or 2", fn, mode);
+  } else if (mode != 0) {
+    return set_error(kErrInvalid, "%s: mode=%d of stage %d is not 0", fn, mode, stage);
+  }
+  const WideFitCtx c = wide_fit_ctx(desc, p);
+  return wide_fit_stage(c, iter, stage, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -371,28 +371,57 @@ static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
   return kOk;
 }
 
-static int wmf_run(const fgp_wide_mt_fit_desc* a, const WmfPlan& p, int iter0, int iters, int final_no_update,
-                   hipStream_t st) {
-  const WmfLay& m = p.lay;
-  const int T = m.T, np = m.np, d = a->d;
+// One iteration as stages, in the order wmf_run enqueues them.  fgp_wide_mt_fit_stage (a test hook) enqueues one of them;
+// wmf_run is the loop over the same function, so the run and the staged sequence are one piece of code.
+enum WmfStage {
+  kWmsPrologue = 0,   // k_wide_mt_fit_step in mode 0; the stage's mode is its init flag
+  kWmsK1,             // fgp_wide_mt_k1 of every pair
+  kWmsForward,        // lambda = ft(k1), one batched call per sorted task
+  kWmsLams,           // k_wide_mt_lams
+  kWmsBlocks,         // fgp_mt_factor, fgp_mt_solve, fgp_mt_selinv, fgp_mt_mll_grad
+  kWmsContract,       // k_wide_mt_contract
+  kWmsAdjoint,        // u = the adjoint transforms of g~
+  kWmsK1Bwd,          // fgp_wide_mt_k1_bwd of every pair
+  kWmsStep,           // k_wide_mt_fit_step in mode 1 or 2
+  kWmsCount
+};
+
+// what every stage needs of the desc and the plan, formed once per run
+struct WmfCtx {
+  const fgp_wide_mt_fit_desc* a;
+  const WmfPlan* p;
+  WmfStep s;
+  Switches sw;
+  double *nat, *gn, *dsl, *A, *logdet, *part, *pb;
+  int* info;
+  char* Bf;
+  void* W;
+  double2 *lams, *fac, *zinv, *glp, *z;
+  const double2* y;
+  size_t esz;                                      // bytes of a lambda element
+};
+
+static WmfCtx wmf_ctx(const fgp_wide_mt_fit_desc* a, const WmfPlan& p) {
+  WmfCtx c{};
+  c.a = a, c.p = &p;
   char* w = static_cast<char*>(a->work);
-  double* nat = reinterpret_cast<double*>(w + p.o_nat);
-  double* gn = reinterpret_cast<double*>(w + p.o_gn);
-  int* info = reinterpret_cast<int*>(w + p.o_info);
-  double* dsl = reinterpret_cast<double*>(w + p.o_dsl);
-  double* A = reinterpret_cast<double*>(w + p.o_a);
-  char* Bf = w + p.o_b;
-  void* W = p.lat ? static_cast<void*>(w + p.o_w) : nullptr;
-  double2* lams = reinterpret_cast<double2*>(w + p.o_lams);
-  double2* fac = reinterpret_cast<double2*>(w + p.o_fac);
-  double2* zinv = reinterpret_cast<double2*>(w + p.o_zinv);
-  double2* glp = reinterpret_cast<double2*>(w + p.o_glp);
-  double2* z = reinterpret_cast<double2*>(w + p.o_z);
-  double* logdet = reinterpret_cast<double*>(w + p.o_ld);
-  double* part = reinterpret_cast<double*>(w + p.o_part);
-  double* pb = reinterpret_cast<double*>(w + p.o_pb);
-  const size_t esz = p.lat ? 16 : 8;                                     // bytes of a lambda element
-  WmfStep s{};
+  c.nat = reinterpret_cast<double*>(w + p.o_nat);
+  c.gn = reinterpret_cast<double*>(w + p.o_gn);
+  c.info = reinterpret_cast<int*>(w + p.o_info);
+  c.dsl = reinterpret_cast<double*>(w + p.o_dsl);
+  c.A = reinterpret_cast<double*>(w + p.o_a);
+  c.Bf = w + p.o_b;
+  c.W = p.lat ? static_cast<void*>(w + p.o_w) : nullptr;
+  c.lams = reinterpret_cast<double2*>(w + p.o_lams);
+  c.fac = reinterpret_cast<double2*>(w + p.o_fac);
+  c.zinv = reinterpret_cast<double2*>(w + p.o_zinv);
+  c.glp = reinterpret_cast<double2*>(w + p.o_glp);
+  c.z = reinterpret_cast<double2*>(w + p.o_z);
+  c.logdet = reinterpret_cast<double*>(w + p.o_ld);
+  c.part = reinterpret_cast<double*>(w + p.o_part);
+  c.pb = reinterpret_cast<double*>(w + p.o_pb);
+  c.esz = p.lat ? 16 : 8;
+  WmfStep& s = c.s;
   s.f.n_params = p.n_params;
   s.f.raw = a->raw;
   s.f.prev = a->rprop_prev;
@@ -403,92 +432,112 @@ static int wmf_run(const fgp_wide_mt_fit_desc* a, const WmfPlan& p, int iter0, i
   s.f.scale_rg = a->rg_scale, s.f.ls_rg = a->rg_ls, s.f.noise_rg = a->rg_noise;
   s.f.mll_const = a->mll_const;
   s.f.eta_minus = a->eta_minus, s.f.eta_plus = a->eta_plus, s.f.step_min = a->step_min, s.f.step_max = a->step_max;
-  s.lay = m;
-  s.d = d, s.dl = a->dl, s.B = a->B, s.nbx = p.nbx;
+  s.lay = p.lay;
+  s.d = a->d, s.dl = a->dl, s.B = a->B, s.nbx = p.nbx;
   s.rg_factor = a->rg_factor, s.rg_vtask = a->rg_vtask;
   s.w = a->logdet_weight, s.lr = a->lr;
-  s.part = part, s.dsl = dsl, s.nat = nat, s.gn = gn, s.info = info;
-  const Switches sw = read_switches();
+  s.part = c.part, s.dsl = c.dsl, s.nat = c.nat, s.gn = c.gn, s.info = c.info;
+  c.sw = read_switches();
+  c.y = static_cast<const double2*>(a->y);
+  return c;
+}
+
+// Stage `stage` of iteration `iter` (the history row the step writes).  mode: the prologue's init flag, the step's mode
+// (1 or 2), otherwise unused.  The caller has validated stage and mode.
+static int wmf_stage(const WmfCtx& c, int iter, int stage, int mode, hipStream_t st) {
+  const fgp_wide_mt_fit_desc* a = c.a;
+  const WmfPlan& p = *c.p;
+  const WmfLay& m = p.lay;
+  const int T = m.T, np = m.np, d = a->d;
   const fgp_mt_layout* lay = &a->layout;
-  const double2* y = static_cast<const double2*>(a->y);
-  auto step = [&](int iter, int mode, int init) {
-    k_wide_mt_fit_step<<<1, kWG, 0, st>>>(s, iter, mode, init);
-    return check_launch("k_wide_mt_fit_step");
-  };
-  int rc = step(0, 0, iter0 == 0 && a->lr > 0.0);
+  double *nat = c.nat, *A = c.A;
+  int rc = kOk;
+  switch (stage) {
+    case kWmsPrologue:
+      k_wide_mt_fit_step<<<1, kWG, 0, st>>>(c.s, 0, 0, mode);
+      return check_launch("k_wide_mt_fit_step");
+    case kWmsK1:
+      // k1 of every pair into A at the pair's packed offset: the pairs that share k lie contiguously
+      for (int k = 0, q = 0; k < T && rc == kOk; ++k)
+        for (int l = k; l < T && rc == kOk; ++l, ++q)
+          rc = fgp_wide_mt_k1(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
+                              A + m.offk[k] + (int64_t)(l - k) * m.n[k], st);
+      return rc;
+    case kWmsForward:
+      // lambda = ft(k1), stable (AbstractFastGP.ft), the T - k rows of sorted task k in one call
+      for (int k = 0; k < T && rc == kOk; ++k) {
+        const int64_t n = m.n[k], rows = T - k;
+        const int lg = p.log2n[k];
+        double* in = A + m.offk[k];
+        void* out = c.Bf + c.esz * (size_t)m.offk[k];
+        if (!p.lat) rc = fgp_fwht(in, n, static_cast<double*>(out), rows, lg, 1, st);
+        else if (use_r2c(c.sw, true, lg)) rc = fgp_fftbr_real(in, n, out, c.W, rows, lg, st);
+        else rc = fgp_fftbr(in, n, 1, out, rows, lg, 1, st);
+      }
+      return rc;
+    case kWmsLams: {
+      const dim3 gl((unsigned)p.nbx, (unsigned)np);
+      if (p.lat) k_wide_mt_lams<0><<<gl, kWG, 0, st>>>(m, a->raw, c.Bf, c.lams);
+      else k_wide_mt_lams<1><<<gl, kWG, 0, st>>>(m, a->raw, c.Bf, c.lams);
+      return check_launch("k_wide_mt_lams");
+    }
+    case kWmsBlocks:
+      // the structured factor, the solves of the B vectors, the selected inverse and dL/dlams (fgp_multitask.hip); a
+      // non-positive pivot sets info and counts as log|pivot|, as in the generic loop and MtGeneralEngine
+      rc = fgp_mt_factor(lay, c.lams, 1, c.fac, c.logdet, c.info, st);
+      if (rc == kOk) rc = fgp_mt_solve(lay, c.fac, 1, c.y, p.rn, a->B, c.z, st);
+      if (rc == kOk) rc = fgp_mt_selinv(lay, c.fac, 1, c.zinv, st);
+      if (rc == kOk) rc = fgp_mt_mll_grad(lay, c.zinv, c.z, c.gn, c.gn + a->B, a->B, 1, c.glp, st);
+      return rc;
+    case kWmsContract: {
+      const dim3 gc((unsigned)p.nbx, (unsigned)np + 1);
+      if (p.lat)
+        k_wide_mt_contract<0><<<gc, kWG, 0, st>>>(m, a->raw, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet, p.nbx,
+                                                  c.part);
+      else
+        k_wide_mt_contract<1><<<gc, kWG, 0, st>>>(m, a->raw, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet, p.nbx,
+                                                  c.part);
+      return check_launch("k_wide_mt_contract");
+    }
+    case kWmsAdjoint:
+      // u = dL/dk1: the adjoint transform of g~ (lattice: the real part), batched as the forward
+      for (int k = 0; k < T && rc == kOk; ++k) {
+        const int64_t n = m.n[k], rows = T - k;
+        const int lg = p.log2n[k];
+        double* out = A + m.offk[k];
+        void* in = c.Bf + c.esz * (size_t)m.offk[k];
+        if (!p.lat) rc = fgp_fwht(static_cast<const double*>(in), n, out, rows, lg, 1, st);
+        else if (use_r2c(c.sw, true, lg)) rc = fgp_ifftbr_real(in, n, nullptr, 0, out, n, c.W, rows, lg, st);
+        else rc = fgp_ifftbr(in, n, out, 1, c.W, rows, lg, 1, st);
+      }
+      return rc;
+    case kWmsK1Bwd:
+      for (int k = 0, q = 0; k < T && rc == kOk; ++k)
+        for (int l = k; l < T && rc == kOk; ++l, ++q)
+          rc = fgp_wide_mt_k1_bwd(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
+                                  A + m.offk[k] + (int64_t)(l - k) * m.n[k], c.dsl + (int64_t)q * (1 + d),
+                                  c.dsl + (int64_t)q * (1 + d) + 1, c.pb, st);
+      return rc;
+    default:
+      k_wide_mt_fit_step<<<1, kWG, 0, st>>>(c.s, iter, mode, 0);
+      return check_launch("k_wide_mt_fit_step");
+  }
+}
+
+static int wmf_run(const fgp_wide_mt_fit_desc* a, const WmfPlan& p, int iter0, int iters, int final_no_update,
+                   hipStream_t st) {
+  const WmfCtx c = wmf_ctx(a, p);
+  int rc = wmf_stage(c, 0, kWmsPrologue, iter0 == 0 && a->lr > 0.0, st);
   for (int it = 0; it < iters && rc == kOk; ++it) {
-    // k1 of every pair into A at the pair's packed offset: the pairs that share k lie contiguously
-    for (int k = 0, q = 0; k < T && rc == kOk; ++k)
-      for (int l = k; l < T && rc == kOk; ++l, ++q)
-        rc = fgp_wide_mt_k1(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
-                            A + m.offk[k] + (int64_t)(l - k) * m.n[k], st);
-    // lambda = ft(k1), stable (AbstractFastGP.ft), the T - k rows of sorted task k in one call
-    for (int k = 0; k < T && rc == kOk; ++k) {
-      const int64_t n = m.n[k], rows = T - k;
-      const int lg = p.log2n[k];
-      double* in = A + m.offk[k];
-      void* out = Bf + esz * (size_t)m.offk[k];
-      if (!p.lat) rc = fgp_fwht(in, n, static_cast<double*>(out), rows, lg, 1, st);
-      else if (use_r2c(sw, true, lg)) rc = fgp_fftbr_real(in, n, out, W, rows, lg, st);
-      else rc = fgp_fftbr(in, n, 1, out, rows, lg, 1, st);
-    }
-    if (rc != kOk) break;
-    const dim3 gl((unsigned)p.nbx, (unsigned)np), gc((unsigned)p.nbx, (unsigned)np + 1);
-    if (p.lat) k_wide_mt_lams<0><<<gl, kWG, 0, st>>>(m, a->raw, Bf, lams);
-    else k_wide_mt_lams<1><<<gl, kWG, 0, st>>>(m, a->raw, Bf, lams);
-    rc = check_launch("k_wide_mt_lams");
-    // the structured factor, the solves of the B vectors, the selected inverse and dL/dlams (fgp_multitask.hip); a
-    // non-positive pivot sets info and counts as log|pivot|, as in the generic loop and MtGeneralEngine
-    if (rc == kOk) rc = fgp_mt_factor(lay, lams, 1, fac, logdet, info, st);
-    if (rc == kOk) rc = fgp_mt_solve(lay, fac, 1, y, p.rn, a->B, z, st);
-    if (rc == kOk) rc = fgp_mt_selinv(lay, fac, 1, zinv, st);
-    if (rc == kOk) rc = fgp_mt_mll_grad(lay, zinv, z, gn, gn + a->B, a->B, 1, glp, st);
-    if (rc != kOk) break;
-    if (p.lat) k_wide_mt_contract<0><<<gc, kWG, 0, st>>>(m, a->raw, glp, Bf, y, z, (int64_t)a->B * p.rn, logdet, p.nbx, part);
-    else k_wide_mt_contract<1><<<gc, kWG, 0, st>>>(m, a->raw, glp, Bf, y, z, (int64_t)a->B * p.rn, logdet, p.nbx, part);
-    rc = check_launch("k_wide_mt_contract");
-    // u = dL/dk1: the adjoint transform of g~ (lattice: the real part), batched as the forward
-    for (int k = 0; k < T && rc == kOk; ++k) {
-      const int64_t n = m.n[k], rows = T - k;
-      const int lg = p.log2n[k];
-      double* out = A + m.offk[k];
-      void* in = Bf + esz * (size_t)m.offk[k];
-      if (!p.lat) rc = fgp_fwht(static_cast<const double*>(in), n, out, rows, lg, 1, st);
-      else if (use_r2c(sw, true, lg)) rc = fgp_ifftbr_real(in, n, nullptr, 0, out, n, W, rows, lg, st);
-      else rc = fgp_ifftbr(in, n, out, 1, W, rows, lg, 1, st);
-    }
-    for (int k = 0, q = 0; k < T && rc == kOk; ++k)
-      for (int l = k; l < T && rc == kOk; ++l, ++q)
-        rc = fgp_wide_mt_k1_bwd(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
-                                A + m.offk[k] + (int64_t)(l - k) * m.n[k], dsl + (int64_t)q * (1 + d),
-                                dsl + (int64_t)q * (1 + d) + 1, pb, st);
-    if (rc != kOk) break;
     const bool last = it + 1 == iters;
-    rc = step(iter0 + it, (last && final_no_update) ? 1 : 2, 0);
+    for (int stage = kWmsK1; stage < kWmsCount && rc == kOk; ++stage)
+      rc = wmf_stage(c, iter0 + it, stage, stage == kWmsStep ? ((last && final_no_update) ? 1 : 2) : 0, st);
   }
   return rc;
 }
 
-}  // namespace fgp
-
-using namespace fgp;
-
-extern "C" {
-
-int fgp_wide_mt_fit_work(const fgp_wide_mt_fit_desc* desc, int64_t* bytes) {
-  WmfPlan p;
-  int rc = wmf_plan("fgp_wide_mt_fit_work", desc, p);
-  if (rc != kOk) return rc;
-  if (!bytes) return set_error(kErrInvalid, "fgp_wide_mt_fit_work: null pointer: bytes");
-  *bytes = (int64_t)p.bytes;
-  return kOk;
-}
-
-int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {
-  static const char* fn = "fgp_wide_mt_fit_run";
-  WmfPlan p;
-  int rc = wmf_plan(fn, desc, p);
-  if (rc != kOk) return rc;
+// what fgp_wide_mt_fit_run and fgp_wide_mt_fit_stage validate beyond the plan
+static int wmf_check(const char* fn, const fgp_wide_mt_fit_desc* desc, const WmfPlan& p) {
   const struct {
     const void* ptr;
     const char* name;
@@ -512,12 +561,71 @@ int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, 
       if (pr.ind[e] != 0 && pr.ind[e] != 1)
         return set_error(kErrInvalid, "%s: pair[%d].ind[%d][%d]=%d is not 0 or 1", fn, q, e / desc->d, e % desc->d, pr.ind[e]);
   }
+  return kOk;
+}
+
+}  // namespace fgp
+
+using namespace fgp;
+
+extern "C" {
+
+int fgp_wide_mt_fit_work(const fgp_wide_mt_fit_desc* desc, int64_t* bytes) {
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_work", desc, p);
+  if (rc != kOk) return rc;
+  if (!bytes) return set_error(kErrInvalid, "fgp_wide_mt_fit_work: null pointer: bytes");
+  *bytes = (int64_t)p.bytes;
+  return kOk;
+}
+
+int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {
+  static const char* fn = "fgp_wide_mt_fit_run";
+  WmfPlan p;
+  int rc = wmf_plan(fn, desc, p);
+  if (rc != kOk) return rc;
+  rc = wmf_check(fn, desc, p);
+  if (rc != kOk) return rc;
   if (iters < 0) return set_error(kErrInvalid, "%s: iters=%d negative", fn, iters);
   if (iter0 < 0) return set_error(kErrInvalid, "%s: iter0=%d negative", fn, iter0);
   if (((uintptr_t)desc->y | (uintptr_t)desc->work) & 15)
     return set_error(kErrInvalid, "%s: y and work must be 16-byte aligned", fn);
   if (iters == 0) return kOk;
   return wmf_run(desc, p, iter0, iters, final_no_update, (hipStream_t)stream);
+}
+
+int fgp_wide_mt_fit_work_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[15]) {
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_work_layout", desc, p);
+  if (rc != kOk) return rc;
+  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_work_layout: null pointer: offsets");
+  const size_t o[15] = {p.o_nat,  p.o_gn,   p.o_info, p.o_dsl, p.o_a,  p.o_b,    p.o_w, p.o_lams,
+                        p.o_fac, p.o_zinv, p.o_glp,  p.o_z,   p.o_ld, p.o_part, p.o_pb};
+  for (int i = 0; i < 15; ++i) offsets[i] = (int64_t)o[i];
+  return kOk;
+}
+
+int fgp_wide_mt_fit_stage(const fgp_wide_mt_fit_desc* desc, int iter, int stage, int mode, void* stream) {
+  static const char* fn = "fgp_wide_mt_fit_stage";
+  WmfPlan p;
+  int rc = wmf_plan(fn, desc, p);
+  if (rc != kOk) return rc;
+  rc = wmf_check(fn, desc, p);
+  if (rc != kOk) return rc;
+  if (((uintptr_t)desc->y | (uintptr_t)desc->work) & 15)
+    return set_error(kErrInvalid, "%s: y and work must be 16-byte aligned", fn);
+  if (iter < 0) return set_error(kErrInvalid, "%s: iter=%d negative", fn, iter);
+  if (stage < 0 || stage >= kWmsCount) return set_error(kErrInvalid, "%s: stage=%d outside 0..%d", fn, stage, kWmsCount - 1);
+  if (stage == kWmsPrologue) {
+    if (mode != 0 && mode != 1) return set_error(kErrInvalid, "%s: mode=%d of the prologue is not 0 or 1 (init)", fn, mode);
+    if (mode == 1 && !(desc->lr > 0.0)) return set_error(kErrInvalid, "%s: mode=1 (init) needs lr > 0", fn);
+  } else if (stage == kWmsStep) {
+    if (mode != 1 && mode != 2) return set_error(kErrInvalid, "%s: mode=%d of the step is not 1 or 2", fn, mode);
+  } else if (mode != 0) {
+    return set_error(kErrInvalid, "%s: mode=%d of stage %d is not 0", fn, mode, stage);
+  }
+  const WmfCtx c = wmf_ctx(desc, p);
+  return wmf_stage(c, iter, stage, mode, (hipStream_t)stream);
 }
 
 }  // extern "C"

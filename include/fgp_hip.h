@@ -591,6 +591,23 @@ extern int fgp_wide_fit_work(const fgp_wide_fit_desc* desc, int64_t* len);
  * cv_weight under FGP_LOSS_CV, a null pointer and negative iters each return FGP_ERR_INVALID with a message that
  * names the field. */
 extern int fgp_wide_fit_run(const fgp_wide_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream);
+/* Addition to ABI 20 -- test hooks (no reference counterpart).
+ * fgp_wide_fit_work_layout: the offsets IN DOUBLES into `work` of { nat_scale [G], nat_ls [G][d], dscale [G], dls [G][d],
+ * A [G][n] (k1, then u = dL/dk1), B [G][n] complex128 (lattice) / float64 (net) (lambda, then g~), W (the lattice
+ * transforms' scratch, empty for nets), pe [G][3][nbe] (k_wide_fit_eig's partials, nbe = ceil(n / 2048)), pb
+ * (fgp_wide_k1_bwd's partials), pl [G][4][nbe] (the GCV / CV partials; = fgp_wide_fit_work's length under the MLL) },
+ * ascending and even.  The desc is validated as fgp_wide_fit_work validates it; no pointer of it is followed and no HIP
+ * call is made; NULL offsets returns FGP_ERR_INVALID.
+ * fgp_wide_fit_stage enqueues exactly ONE stage of the sequence fgp_wide_fit_run enqueues per iteration (the run is the
+ * loop over the same function), so that a test can read an intermediate before the next stage overwrites it:
+ *   stage 0  prologue: the step kernel in mode 0; `mode` = 1 starts a new fit (prev = 0, step = lr; needs lr > 0), 0 not
+ *         1  k1        2  the forward transform        3  terms: the eigenvalue terms (GCV / CV: the partial sums)
+ *         4  terms-2: g~ under GCV / CV (FGP_ERR_INVALID under the MLL)        5  the adjoint transform
+ *         6  k1_bwd    7  step: `mode` = 1 (evaluate) or 2 (and update), history row `iter`
+ * `mode` is 0 for every other stage.  The desc is validated as fgp_wide_fit_run validates it, and a stage, mode or iter
+ * outside the above returns FGP_ERR_INVALID, all before any HIP call. */
+extern int fgp_wide_fit_work_layout(const fgp_wide_fit_desc* desc, int64_t offsets[10]);
+extern int fgp_wide_fit_stage(const fgp_wide_fit_desc* desc, int iter, int stage, int mode, void* stream);
 
 /* Addition to ABI 20 -- fgp_post_var_qf / the quadratic form of fgp_post_var_batched for wide d:
  *   out[p, t] = sum_k wa_p[k] |ft(K_p(xt_p[t], z_p))_k|^2   for 9 <= d <= 64, 13 <= log2n <= 24,
@@ -905,6 +922,19 @@ extern int (fgp_wide_mt_fit_work)(const fgp_wide_mt_fit_desc* desc, int64_t* byt
  * declarations as the fixed set of the task-pair kernel's entry points.) */
 extern int (fgp_wide_mt_fit_run)(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update,
                                  void* stream);
+/* Addition to ABI 20 -- test hooks (no reference counterpart), as fgp_wide_fit_work_layout / fgp_wide_fit_stage.
+ * fgp_wide_mt_fit_work_layout: the BYTE offsets into `work` of { nat [1 + d], gn [B + 1] (gn, then gl), info (int),
+ * dsl [np][1 + d], A [L] (k1, then u), B [L] complex128 (lattice) / float64 (net) (lambda, then g~), W (the lattice
+ * transforms' scratch, empty for nets), lams, fac, zinv, glp [L] complex128, z [B][R nmin] complex128, logdet [nmin],
+ * part [np + 1][2][nbx] (nbx = ceil(n_0 / 256)), pb (fgp_wide_mt_k1_bwd's partials) }, each a multiple of 256,
+ * ascending.  Validated as fgp_wide_mt_fit_work; no pointer is followed, no HIP call is made.
+ * fgp_wide_mt_fit_stage enqueues ONE stage of fgp_wide_mt_fit_run's iteration (the run is the loop over it):
+ *   stage 0  prologue (`mode` = 1: a new fit, needs lr > 0)     1  k1 of every pair     2  the forward transforms
+ *         3  lams     4  the four block calls (factor, solve, selected inverse, gradient)     5  contract
+ *         6  the adjoint transforms     7  k1_bwd of every pair     8  step, `mode` = 1 or 2, history row `iter`
+ * Validation as fgp_wide_mt_fit_run's, and of stage / mode / iter, before any HIP call (FGP_ERR_INVALID). */
+extern int (fgp_wide_mt_fit_work_layout)(const fgp_wide_mt_fit_desc* desc, int64_t offsets[15]);
+extern int (fgp_wide_mt_fit_stage)(const fgp_wide_mt_fit_desc* desc, int iter, int stage, int mode, void* stream);
 
 /* ABI 15 -- consistency check of the fused spectral fit's last-arriver hand-off (a test hook, no reference
  * counterpart).  enable != 0 arms it for the following fgp_fit_run calls: every wave of the one-launch

@@ -1,4 +1,7 @@
-"""Shared helpers for the GPU parity tests: build product GPs from the golden fixtures."""
+"""Shared helpers for the GPU parity tests: build product GPs from the golden fixtures; device copies, bit comparisons
+and the library's transform-route switch for the stage-by-stage tests."""
+import os
+
 import numpy as np
 import torch
 
@@ -43,3 +46,31 @@ def abs_err(a, b):
     a = torch.as_tensor(a).detach().cpu().reshape(-1)
     b = (b.detach().cpu() if torch.is_tensor(b) else torch.as_tensor(np.asarray(b))).reshape(-1)
     return float((a - b).abs().max()) if b.numel() else 0.0
+
+
+def to_dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+def to_np(t):
+    return t.cpu().numpy().copy()
+
+
+def raw_stream():
+    from fastgaussianprocesses_amd import _native as N
+    return N.stream_ptr(torch.device(DEV, torch.cuda.current_device()))
+
+
+def bits(t):
+    """The bytes of a tensor of any dtype and stride, as a flat uint8 tensor."""
+    return torch.empty(t.numel(), dtype=t.dtype, device=t.device).copy_(t.reshape(-1)).view(torch.uint8)
+
+
+def same_bits(a, b):
+    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
+
+
+def uses_r2c(lattice, log2n):
+    """use_r2c(read_switches(), ...) of csrc/fgp_runtime.h: the half-length lattice transforms from n = 2^17 unless
+    FGP_R2C starts with '0' (the library reads the same variable at every call)."""
+    return bool(lattice) and log2n >= 17 and os.environ.get("FGP_R2C", "")[:1] != "0"
