@@ -347,6 +347,86 @@ __global__ __launch_bounds__(kWG) void k_wmt_rows_zip(const double* __restrict__
     if (g0 + b < Gk) rows[(int64_t)(g0 + b) * N + t] = hyp[(int64_t)(g0 + b) * (1 + d)] * acc[b];
 }
 
+// ------------------------------------------------------------------------------------------------ posterior mean
+// partial[b][t][c] = sum_{i in chunk c} K^{(g(b))}(xt_t, z_i) coeffs[b][i] of one task pair, no kernel row stored.
+// k_wmt_rows' mapping: thread = training point, striding through the chunk in steps of kWG; workgroup = (chunk c, test
+// point t, NB output rows).  The pair's value is wmt_rows_pair's and then the scale, the bits k_wmt_rows writes; a thread
+// adds its points in ascending i with sum = fma(K, c_i, sum), block_sum adds the threads.  NK kernel rows per workgroup:
+// 1 when every output row shares the hyper-parameters (Gk == 1: the kernel is evaluated once for the NB rows), else NB.
+// A row past B repeats row B - 1 and is not stored.  The chunk bounds depend on n and the chunk length alone.
+constexpr int kMtPmB = 4;                   // output rows per workgroup
+constexpr int64_t kMtPmChunk = 1024;        // default chunk of training points: 4 per thread
+constexpr int64_t kMtPmNt = 65535;          // test points per launch (grid.y)
+
+template <int FAM, int NK, int NB>
+__global__ __launch_bounds__(kWG) void k_wmt_post_mean(const double* __restrict__ xt, int64_t N,
+                                                       const void* __restrict__ z, int64_t n, int d, int P,
+                                                       const MtTables* __restrict__ tab, MtCc cc, int tbits,
+                                                       const double* __restrict__ hyp, int Gk,
+                                                       const double* __restrict__ coeffs, int64_t cstride, int B,
+                                                       int64_t chunk, int64_t nchunks, double* __restrict__ partial) {
+  static_assert(NK == 1 || NK == NB, "one kernel row for all output rows, or one each");
+  __shared__ MtRowsLds<NK> s;
+  __shared__ double xs[kWD];
+  __shared__ double red[kWG / 64];
+  const int tid = threadIdx.x;
+  const int64_t t = blockIdx.y;
+  const int b0 = blockIdx.z * NB;
+  wmt_rows_tables<NK>(s, tab, P, d, hyp, NK == 1 ? 0 : b0, Gk);
+  if (tid < d) {
+    const double v = xt[t * d + tid];
+    if constexpr (FAM == 0) xs[tid] = v;
+    else xs[tid] = __longlong_as_double((long long)to_bits(v, tbits));
+  }
+  __syncthreads();
+  double sc[NK], sum[NB];
+  const double* cb[NB];
+#pragma unroll
+  for (int k = 0; k < NK; ++k) {
+    const int g = NK == 1 ? 0 : (b0 + k < Gk ? b0 + k : Gk - 1);
+    sc[k] = hyp[(int64_t)g * (1 + d)];
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    sum[b] = 0.0;
+    cb[b] = coeffs + (int64_t)(b0 + b < B ? b0 + b : B - 1) * cstride;
+  }
+  const int64_t i0 = (int64_t)blockIdx.x * chunk;
+  const int64_t i1 = i0 + chunk < n ? i0 + chunk : n;
+  for (int64_t i = i0 + tid; i < i1; i += kWG) {
+    double acc[NK];
+    wmt_rows_pair<FAM, NK>(s, cc, P, d, tbits, [&](int j) { return xs[j]; }, z, n, i, acc);
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int k = NK == 1 ? 0 : b;
+      sum[b] = __builtin_fma(sc[k] * acc[k], cb[b][i], sum[b]);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    const double v = block_sum(sum[b], red);
+    if (tid == 0 && b0 + b < B) partial[((int64_t)(b0 + b) * N + t) * nchunks + blockIdx.x] = v;
+  }
+}
+
+// out[b][t] = beta out[b][t] + w[b] sum_c partial[b][t][c]: one workgroup per output, a lane over every kWG-th chunk in
+// ascending order, then block_sum's fixed tree (k_wide_sum); w NULL: 1; beta 0 (out is not read) or 1
+__global__ __launch_bounds__(kWG) void k_wmt_post_mean_sum(const double* __restrict__ partial, int64_t nchunks, int64_t N,
+                                                           const double* __restrict__ w, int beta,
+                                                           double* __restrict__ out, int64_t out_stride) {
+  __shared__ double red[kWG / 64];
+  const int64_t t = blockIdx.x, b = blockIdx.y;
+  const double* p = partial + (b * N + t) * nchunks;
+  double s = 0.0;
+  for (int64_t c = threadIdx.x; c < nchunks; c += kWG) s += p[c];
+  s = block_sum(s, red);
+  if (threadIdx.x == 0) {
+    const double v = w ? w[b] * s : s;
+    double* o = out + b * out_stride + t;
+    *o = beta ? *o + v : v;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 // argument checks shared by the entry points (before any HIP call)
 static int wmt_dp_ok(const char* fn, int d, int P) {
@@ -566,6 +646,96 @@ int fgp_wide_mt_rows(int family, const double* xt, int64_t N, const void* z, int
   FGP_WMT(k_wmt_rows, grid, xt, N, z, n, d, P, dt, c, tbits, hyp, Gk, rows);
 #undef FGP_WMT
   return check_launch("k_wmt_rows");
+}
+
+// the chunk of training points of fgp_mt_wide_post_mean: 0 = the default, else a positive multiple of kWG
+static int wmt_pm_sizes(const char* fn, int64_t N, int64_t n, int B, int64_t chunk, int64_t* chunk_out,
+                        int64_t* nchunks) {
+  if (N < 0) return set_error(kErrInvalid, "%s: N=%lld is negative", fn, (long long)N);
+  if (n < 1) return set_error(kErrInvalid, "%s: n=%lld (at least 1 training point)", fn, (long long)n);
+  if (B < 1 || B > 65535) return set_error(kErrInvalid, "%s: B=%d outside 1..65535", fn, B);
+  if (chunk < 0 || chunk % kWG != 0)
+    return set_error(kErrInvalid, "%s: chunk=%lld is not 0 (default) or a positive multiple of %d", fn, (long long)chunk, kWG);
+  const int64_t ch = chunk ? chunk : kMtPmChunk;
+  const int64_t nc = (n - 1) / ch + 1;
+  if (nc > 0x7fffffffll) return set_error(kErrUnsupported, "%s: n=%lld needs %lld chunks", fn, (long long)n, (long long)nc);
+  *chunk_out = ch;
+  *nchunks = nc;
+  return kOk;
+}
+
+int fgp_mt_wide_post_mean_work(int64_t N, int64_t n, int B, int64_t chunk, int64_t* len) {
+  static const char* fn = "fgp_mt_wide_post_mean_work";
+  int64_t ch = 0, nc = 0;
+  int rc = wmt_pm_sizes(fn, N, n, B, chunk, &ch, &nc);
+  if (rc != kOk) return rc;
+  if (!len) return set_error(kErrInvalid, "%s: null pointer (len)", fn);
+  *len = std::max<int64_t>(1, (int64_t)B * std::min<int64_t>(N, kMtPmNt) * nc);
+  return kOk;
+}
+
+int fgp_mt_wide_post_mean(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int P,
+                          const int* order, const double* coef, const double* add, const int* ind, const double* cc,
+                          int tbits, const double* hyp, int Gk, const double* coeffs, int64_t coeff_stride, int B,
+                          const double* w, int beta, double* out, int64_t out_stride, double* work, int64_t chunk,
+                          void* stream) {
+  static const char* fn = "fgp_mt_wide_post_mean";
+  int rc = wmt_dp_ok(fn, d, P);
+  if (rc != kOk) return rc;
+  int64_t ch = 0, nchunks = 0;
+  rc = wmt_pm_sizes(fn, N, n, B, chunk, &ch, &nchunks);
+  if (rc != kOk) return rc;
+  if (Gk != 1 && Gk != B) return set_error(kErrInvalid, "%s: Gk=%d is neither 1 nor B=%d", fn, Gk, B);
+  if (beta != 0 && beta != 1) return set_error(kErrInvalid, "%s: beta=%d is not 0 or 1", fn, beta);
+  if (coeff_stride < (B > 1 ? n : 0))
+    return set_error(kErrInvalid, "%s: coeff_stride=%lld below n=%lld", fn, (long long)coeff_stride, (long long)n);
+  if (out_stride < (B > 1 ? N : 0))
+    return set_error(kErrInvalid, "%s: out_stride=%lld below N=%lld", fn, (long long)out_stride, (long long)N);
+  if (!xt) return set_error(kErrInvalid, "%s: null pointer (xt)", fn);
+  if (!z) return set_error(kErrInvalid, "%s: null pointer (z)", fn);
+  if (!hyp) return set_error(kErrInvalid, "%s: null pointer (hyp)", fn);
+  if (!coeffs) return set_error(kErrInvalid, "%s: null pointer (coeffs)", fn);
+  if (!out) return set_error(kErrInvalid, "%s: null pointer (out)", fn);
+  if (!work) return set_error(kErrInvalid, "%s: null pointer (work)", fn);
+  MtInd is;
+  rc = wmt_ind(fn, d, P, ind, cc, is);
+  if (rc != kOk) return rc;
+  static thread_local MtTables tab;
+  rc = wmt_tables(fn, family, d, P, order, coef, add, ind, tbits, tab);
+  if (rc != kOk) return rc;
+  if (N == 0) return kOk;
+  MtCc c;
+  for (int p = 0; p < kMtP; ++p) c.cc[p] = is.cc[p];
+  const MtTables* dt = nullptr;
+  rc = wmt_device_tables(fn, tab, &dt);
+  if (rc != kOk) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  const bool lat = family == FGP_FAMILY_LATTICE;
+  const unsigned gz = B == 1 ? 1u : (unsigned)((B + kMtPmB - 1) / kMtPmB);
+  // the test points in launches of at most kMtPmNt: a point's chunks and their order do not depend on the split
+  for (int64_t t0 = 0; t0 < N; t0 += kMtPmNt) {
+    const int64_t Nc = std::min<int64_t>(kMtPmNt, N - t0);
+    const dim3 grid((unsigned)nchunks, (unsigned)Nc, gz);
+#define FGP_WMT_PM(FAM, NK, NB)                                                                                          \
+  k_wmt_post_mean<FAM, NK, NB><<<grid, kWG, 0, st>>>(xt + t0 * d, Nc, z, n, d, P, dt, c, tbits, hyp, Gk, coeffs, coeff_stride, \
+                                                      B, ch, nchunks, work)
+    if (lat) {
+      if (B == 1) FGP_WMT_PM(0, 1, 1);
+      else if (Gk == 1) FGP_WMT_PM(0, 1, kMtPmB);
+      else FGP_WMT_PM(0, kMtPmB, kMtPmB);
+    } else {
+      if (B == 1) FGP_WMT_PM(1, 1, 1);
+      else if (Gk == 1) FGP_WMT_PM(1, 1, kMtPmB);
+      else FGP_WMT_PM(1, kMtPmB, kMtPmB);
+    }
+#undef FGP_WMT_PM
+    rc = check_launch("k_wmt_post_mean");
+    if (rc != kOk) return rc;
+    k_wmt_post_mean_sum<<<dim3((unsigned)Nc, (unsigned)B), kWG, 0, st>>>(work, nchunks, Nc, w, beta, out + t0, out_stride);
+    rc = check_launch("k_wmt_post_mean_sum");
+    if (rc != kOk) return rc;
+  }
+  return kOk;
 }
 
 }  // extern "C"

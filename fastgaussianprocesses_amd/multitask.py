@@ -930,15 +930,65 @@ class MultiTaskFastGP(AbstractFastGP):
         bshape = torch.broadcast_shapes(*[r.shape[:-3] for r in rows])
         return torch.cat([r.expand(bshape + r.shape[-3:]) for r in rows], -3)
 
+    def _post_mean_batch(self):
+        """The batch shape of post_mean: the broadcast of the coefficient batch, the kernel's hyper-parameter rows and
+        the task-kernel batch."""
+        return tuple(torch.broadcast_shapes(self.coeffs.shape[:-1], self._wide_param_rows(),
+                                            self.gram_matrix_tasks.shape[:-2]))
+
+    def _post_mean_mf(self, x, tasks):
+        """m[..., a, t] = sum_l Kt[..., a, l] sum_i K_{a,l}(x_t, xb_{l,i}) coeffs[..., off_l + i] -> [*batch, T', N]
+        without a kernel row (fgp_mt_wide_post_mean, d > 8 and fused specs): one call per (requested task, task with
+        points), accumulated in ascending l; the batch flattened to B rows, the hyper-parameter rows expanded to B when
+        they are more than one and fewer than B."""
+        ns = self._ns
+        xc = x.to(device=self.device, dtype=torch.float64)
+        assert bool(((0 <= xc) & (xc <= 1)).all()), "x should have all elements in [0,1]"
+        bshape = self._post_mean_batch()
+        B = int(np.prod(bshape)) if len(bshape) else 1
+        nsum, Nt, d = sum(ns), xc.shape[0], self.d
+        coeffs = self.coeffs.detach().to(torch.float64)
+        coeffs = coeffs.expand(bshape + (nsum,)).reshape(B, nsum).contiguous()
+        hyp = self._wide_hyp_rows()
+        if hyp.shape[0] > 1 and self._wide_param_rows() != bshape:
+            hyp = hyp.reshape(self._wide_param_rows() + (1 + d,)).expand(bshape + (1 + d,)).reshape(B, 1 + d)
+        Kt = self.gram_matrix_tasks.detach()
+        out = torch.empty((B, len(tasks), Nt), dtype=torch.float64, device=self.device)
+        off = np.concatenate([[0], np.cumsum(ns)])
+        for ai, a in enumerate(tasks):
+            beta = 0
+            for l in range(self.num_tasks):
+                if ns[l] == 0:
+                    continue
+                w = Kt[..., a, l].expand(bshape).reshape(B)
+                ops.mt_wide_post_mean(self._wide_pair_spec(a, l), xc, self._xb_dm(l, ns[l]), hyp,
+                                      coeffs[:, int(off[l]):int(off[l + 1])], w, out[:, ai, :], beta)
+                beta = 1
+            if beta == 0:
+                out[:, ai, :] = 0.0
+        return out.reshape(bshape + (len(tasks), Nt))
+
     def post_mean(self, x, task=None, eval=True):
-        """abstract_gp.py:352-380."""
+        """abstract_gp.py:352-380.  At d > 8, without an autograd graph and with a fused spec for every (requested
+        task, task) pair: the matrix-free sum of _post_mean_mf when the kernel rows [*, T', N, sum n] would exceed 2^22
+        bytes (ops.mt_wide_post_mean_route; FGP_WIDE_MT_POST_MEAN=1 / 0 forces either route), else the rows and an
+        einsum."""
         with (torch.no_grad() if eval else torch.enable_grad() if torch.is_grad_enabled() else torch.no_grad()):
             coeffs = self.coeffs
             assert x.ndim == 2 and x.size(1) == self.d, "x must a torch.Tensor with shape (-1,d)"
             inttask, tasks = self._task_list(task)
             x = x.to(self.device)
-            kmat = self._kmat_rows(x, tasks, self._ns)
-            pmean = torch.einsum("...i,...i->...", kmat, coeffs[..., None, None, :])
+            if ops._wide(self.d) and not self._gradmode() and x.shape[0] > 0 and torch.is_floating_point(x) and all(
+                    self._wide_pair_spec(a, l) is not None for a in tasks for l in range(self.num_tasks)):
+                B = int(np.prod(self._post_mean_batch()))
+                mf = ops.mt_wide_post_mean_route(8 * B * len(tasks) * x.shape[0] * sum(self._ns))
+            else:
+                mf = False
+            if mf:
+                pmean = self._post_mean_mf(x, tasks)
+            else:
+                kmat = self._kmat_rows(x, tasks, self._ns)
+                pmean = torch.einsum("...i,...i->...", kmat, coeffs[..., None, None, :])
         return pmean[..., 0, :] if inttask else pmean
 
     def _check_n(self, n, msg):

@@ -881,6 +881,54 @@ def wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs=False):
     return rows
 
 
+MT_WIDE_POST_MEAN_BYTES = 1 << 22   # default rule of the matrix-free multitask mean: kernel rows beyond this many bytes
+
+
+def mt_wide_post_mean_route(rows_bytes):
+    """The route of a multitask post_mean at d > 8 whose task pairs all have a fused spec: the matrix-free sum
+    (fgp_mt_wide_post_mean) or the kernel rows and an einsum.  FGP_WIDE_MT_POST_MEAN=1: the sum at any size; =0: the rows
+    everywhere (A/B runs); default: the sum when the rows array, rows_bytes = 8 B T' N sum n, exceeds
+    MT_WIDE_POST_MEAN_BYTES.  The rows route allocates that array several times over, so the rule bounds post_mean's
+    memory well inside MT_POST_VAR_QF_BYTES; it stands at 2^22 and not at 2^28 because the sum was measured faster at
+    every size from 1.2 MB to 4.8 GB of rows (no crossover found), and not lower because the
+    routing test of a 60 x 8192 prediction (3.9 MB) counts its fgp_wide_mt_rows calls."""
+    env = os.environ.get("FGP_WIDE_MT_POST_MEAN", "")[:1]
+    if env in ("0", "1"):
+        return env == "1"
+    return rows_bytes > MT_WIDE_POST_MEAN_BYTES
+
+
+def mt_wide_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0):
+    """out[b, t] = beta out[b, t] + w[b] sum_i K_ab^{(g(b))}(xt[t], z[:, i]) coeffs[b, i] in place
+    (fgp_mt_wide_post_mean), no kernel row stored: xt [N, d] float64 test points, z_dn [d, n] dimension-major (float64
+    lattice / int64 net), hyp [Gk, 1 + d] with Gk in {1, B} (g(b) = b or 0), coeffs [B, n] and out [B, N] float64 with
+    unit inner stride (views of wider rows are taken as they are), w [B] or None (1), beta 0 or 1.  chunk: the entry
+    point's chunk of training points (0: its default)."""
+    require_device(xt, "mt_wide_post_mean")
+    xt = xt.to(torch.float64).contiguous()
+    Nt, d = xt.shape
+    n = z_dn.shape[1]
+    assert z_dn.is_contiguous() and z_dn.shape[0] == d == spec.d
+    assert z_dn.dtype == (torch.float64 if spec.family == LATTICE else torch.int64)
+    hyp = hyp.detach().to(torch.float64).contiguous()
+    B = out.shape[0]
+    Gk = hyp.shape[0]
+    assert hyp.shape == (Gk, 1 + d) and Gk in (1, B)
+    assert coeffs.dtype == torch.float64 and coeffs.shape == (B, n) and (n == 1 or coeffs.stride(1) == 1)
+    assert out.dtype == torch.float64 and out.shape == (B, Nt) and (Nt <= 1 or out.stride(1) == 1)
+    if w is not None:
+        w = w.detach().to(torch.float64).reshape(B).contiguous()
+    cs = coeffs.stride(0) if B > 1 else n
+    os_ = out.stride(0) if B > 1 else Nt
+    wlen = ctypes.c_int64(0)
+    N.call("fgp_mt_wide_post_mean_work", Nt, n, B, int(chunk), ctypes.byref(wlen))
+    work = torch.empty((wlen.value,), dtype=torch.float64, device=xt.device)
+    N.call("fgp_mt_wide_post_mean", spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, spec.P, spec.order, spec.coef, spec.add,
+           spec.ind, spec.cc, spec.tbits, N.ptr(hyp), Gk, N.ptr(coeffs), cs, B, N.ptr(w), int(beta), N.ptr(out), os_,
+           N.ptr(work), int(chunk), _stream(xt))
+    return out
+
+
 def mt_factor(lay, lams):
     """Structured LDL^H of G problems' Gram blocks (fgp_mt_factor): lams [G, L] complex128 ->
     (factor [G, L], logdet per frequency class [G, nmin], info [1] int32 device flag)."""

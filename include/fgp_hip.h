@@ -665,6 +665,24 @@ extern int fgp_wide_mt_k1_bwd(const double* parts, int64_t n, int d, int P, cons
 extern int fgp_wide_mt_rows(int family, const double* xt, int64_t N, const void* z, int64_t n, int zip, int d, int P,
                             const int* order, const double* coef, const double* add, const int* ind, const double* cc,
                             int tbits, const double* hyp, int Gk, double* rows, void* stream);
+/* Addition to ABI 20 -- the matrix-free posterior mean of one task pair (a, l), no kernel row stored:
+ *   out[b][t] = beta out[b][t] + w[b] sum_i K_al^{(g(b))}(xt[t], z[:, i]) coeffs[b coeff_stride + i],   b < B, t < N,
+ * g(b) = b if Gk == B, 0 if Gk == 1.  family .. hyp as fgp_wide_mt_rows (K_al before the sum carries the bits that entry
+ * point writes); coeffs [B] rows of n with row stride coeff_stride, w device [B] or NULL (1), beta 0 (out is not read)
+ * or 1, out [B] rows of N with row stride out_stride, all on the device.  Any n >= 1 and N >= 0 (N == 0: FGP_OK, no
+ * launch; test points beyond 65535 are split inside), B <= 65535.  The training points are summed in chunks: a thread
+ * adds every 256th point of a chunk in ascending order, the workgroup its threads in a fixed tree, a second kernel the
+ * chunks (a lane over every 256th chunk in ascending order, the same tree), then w and beta.  chunk: 0 (the default,
+ * 1024) or a positive multiple of 256; the chunk bounds depend on n and chunk alone, so a test point's result carries
+ * the same bits predicted alone or among others.  work: fgp_mt_wide_post_mean_work doubles, B min(N, 65535) ceil(n /
+ * chunk).  Validation before any HIP call as above; Gk outside {1, B}, beta outside {0, 1}, a bad chunk or a row
+ * stride below its row: FGP_ERR_INVALID. */
+extern int fgp_mt_wide_post_mean_work(int64_t N, int64_t n, int B, int64_t chunk, int64_t* len);
+extern int fgp_mt_wide_post_mean(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int P,
+                                 const int* order, const double* coef, const double* add, const int* ind,
+                                 const double* cc, int tbits, const double* hyp, int Gk, const double* coeffs,
+                                 int64_t coeff_stride, int B, const double* w, int beta, double* out, int64_t out_stride,
+                                 double* work, int64_t chunk, void* stream);
 
 
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):
