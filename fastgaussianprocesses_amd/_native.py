@@ -139,6 +139,7 @@ class WideMtFitDesc(ctypes.Structure):
         ("eta_minus", _c_dbl), ("eta_plus", _c_dbl), ("step_min", _c_dbl), ("step_max", _c_dbl),
         ("logdet_weight", _c_dbl), ("mll_const", _c_dbl),
         ("loss_hist", _c_vp), ("raw_hist", _c_vp), ("grad_out", _c_vp), ("work", _c_vp),
+        ("loss_metric", _c_int), ("cv_weight", _c_dbl),
     ]
 
 
@@ -260,6 +261,8 @@ _SIGNATURES = {
     "fgp_wide_fit_stage": [_P_WIDEFIT, _c_int, _c_int, _c_int, _c_vp],
     "fgp_wide_mt_fit_work_layout": [_P_WIDEMTFIT, _c_pl],
     "fgp_wide_mt_fit_stage": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
+    # addition to ABI 20: test hook -- where the GCV / CV partials of fgp_wide_mt_fit_run lie in `work`
+    "fgp_wide_mt_fit_loss_layout": [_P_WIDEMTFIT, _c_pl],
 }
 
 

@@ -1,4 +1,4 @@
-// Wide inputs (9 <= d <= 64), multitask / derivative-informed GPs: the device-resident MLL fit loop,
+// Wide inputs (9 <= d <= 64), multitask / derivative-informed GPs: the device-resident fit loop (MLL; GCV / CV),
 // fgp_wide_mt_fit_run (include/fgp_hip.h, an addition to ABI 20) -- AbstractGP.fit's iteration (abstract_gp.py:241-296:
 // loss, loss.backward(), torch.optim.Rprop.step()) over _FastInverseLogDetCache's lams and block inverse
 // (util.py:275-370) for ONE eigen-problem of T sorted tasks, as a fixed sequence of plain launches on the caller's
@@ -16,7 +16,9 @@
 //                                                      raw parameters, Rprop (rprop_update, fgp_nll.h), the natural
 //                                                      scale / lengthscale row of the next k1
 //
-// 3 np + 2 T + 7 entry-point calls per iteration.  No host synchronisation, no device-to-host copy, no atomics, no
+// 3 np + 2 T + 7 entry-point calls per iteration.  fgp_wide_mt_fit_desc.loss_metric GCV / CV (equal n per task) keeps
+// every stage but fgp_mt_mll_grad, which k_wide_mt_loss_sums + k_wide_mt_loss_grad (new, below) replace: one call more.
+// No host synchronisation, no device-to-host copy, no atomics, no
 // inter-workgroup hand-off: every kernel reads what a launch before it wrote.  lam^ = lambda, or conj(lambda) where
 // the pair's conj flag is set (task index a_k > a_l: util.py:280-284).  Nets: lambda and g~ are real (the generic
 // loop's .to(complex128) passes the real part of the gradient back).  fgp_wide_mt_k1 / _k1_bwd take their spec by
@@ -151,6 +153,150 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_contract(WmfLay m, const double
 }
 
 // ------------------------------------------------------------------------------------------------
+// GCV / CV (fgp_wide_mt_fit_desc.loss_metric; util.py:371-394, abstract_gp.py:242-273; the closed forms of T tasks of
+// EQUAL n above k_mt_spec_iter, fgp_spectral.hip).  With equal n every frequency class j < n has one row per task, so the
+// selected inverse zinv IS the dense A_j = Lambda_j^-1 (upper triangle, packed as the lams) and z [B][T n] its solutions.
+//   GCV  N = sum_b sum_j |z_bj|^2, Tr = sum_j Re tr A_j, D = (Tr / (T n))^2, loss = N / D
+//   CV   N_t = sum_b sum_j |z_bjt|^2, S_t = n I_t = sum_j Re A_j[t, t], loss = w n^2 sum_t N_t / S_t^2
+// Both gradients are one form.  With S_rt = sum_b z_r conj(z_t) (per class),
+//   W[r, c] = sum_t ( c2_t A_rt conj(A_ct) - c1_t (S_rt conj(A_ct) + A_rt S_tc) ),      dL = Re tr(W dLambda)
+//   GCV  c1_t = 1 / D, c2_t = 2 N / (D Tr) for every t      (dN = -2 Re(u^H dLambda z), u = A z;  dTr = -Re tr(A^2 dLambda))
+//   CV   c1_t = w n^2 / S_t^2, c2_t = 2 c1_t N_t / S_t      (u = A e_t z_t;  dS_t = -(A e_t)^H dLambda (A e_t))
+// and glp takes fgp_mt_mll_grad's convention: Re W[r, r] on the diagonal, 2 W[r, c] on a coupling entry r < c.
+// The sums are global, so the stage is two kernels: k_wide_mt_loss_sums writes per-workgroup partials
+//   pl [NT][2][nbx] = (N, Tr) (GCV, NT = 1) or (N_t, S_t) per task (CV, NT = T),
+// k_wide_mt_loss_grad re-forms the totals in every workgroup (wmf_total: the same order everywhere, so the same bits)
+// and writes W.  A thread per frequency; the T x T block is never held in registers or LDS: A and z are re-read from
+// global memory (L1 / L2: a wavefront's reads of one entry are contiguous), T (2 B + 3) complex products per entry.
+// FAM 1 (nets): A is real (k_wide_mt_lams writes zero imaginary parts and the factor keeps them), its imaginary parts
+// are not read and their products are dropped -- the bits of the complex form on a zero imaginary part.
+constexpr int kWmfLossQ = 2;
+
+struct WmfCoef {
+  double loss, c1, c2, D;
+};
+
+// GCV: (N, Tr) -> loss, c1, c2, D.  CV: (N_t, S_t) -> task t's term of the loss, c1_t, c2_t.  tn = T n, wn2 = w n^2
+// (exact: n is a power of two).
+__device__ __forceinline__ WmfCoef wmf_loss_coef(bool cv, double N, double S, double tn, double wn2) {
+  WmfCoef c;
+  if (cv) {
+    c.D = S * S;
+    c.c1 = wn2 / c.D;
+    c.loss = c.c1 * N;
+    c.c2 = 2.0 * c.loss / S;
+  } else {
+    const double q = S / tn;
+    c.D = q * q;
+    c.loss = N / c.D;
+    c.c1 = 1.0 / c.D;
+    c.c2 = 2.0 * N / (c.D * S);
+  }
+  return c;
+}
+
+// the second level of one row of partials: a lane over every kWG-th partial in ascending order, then block_sum
+__device__ __forceinline__ double wmf_total(const double* __restrict__ row, int cnt, double* red) {
+  double a = 0.0;
+  for (int c = threadIdx.x; c < cnt; c += kWG) a += row[c];
+  return block_sum(a, red);
+}
+
+// A[r][t] of class j from the packed upper triangle (Z offset by j)
+template <int FAM>
+__device__ __forceinline__ double2 wmf_ainv(const WmfLay& m, const double2* __restrict__ Z, int r, int t) {
+  const int lo = r <= t ? r : t, hi = r <= t ? t : r;
+  const int64_t e = m.offk[lo] + (int64_t)(hi - lo) * m.n[0];
+  if constexpr (FAM == 1) return make_double2(Z[e].x, 0.0);
+  const double2 v = Z[e];
+  return make_double2(v.x, r <= t ? v.y : -v.y);
+}
+template <int FAM>
+__device__ __forceinline__ double2 wmf_a_mulc_a(double2 a, double2 b) {      // a conj(b)
+  if constexpr (FAM == 1) return make_double2(a.x * b.x, 0.0);
+  return cmulc(a, b);
+}
+template <int FAM>
+__device__ __forceinline__ double2 wmf_s_mulc_a(double2 s, double2 a) {      // s conj(a)
+  if constexpr (FAM == 1) return make_double2(s.x * a.x, s.y * a.x);
+  return cmulc(s, a);
+}
+template <int FAM>
+__device__ __forceinline__ double2 wmf_a_mul_s(double2 a, double2 s) {       // a s
+  if constexpr (FAM == 1) return make_double2(a.x * s.x, a.x * s.y);
+  return cmul(a, s);
+}
+
+// blockIdx.x: kWG frequencies; CV: blockIdx.y = task t.  Per thread B ascending (GCV: the tasks ascending inside), then
+// block_sum.
+template <bool CV>
+__global__ __launch_bounds__(kWG) void k_wide_mt_loss_sums(WmfLay m, int B, const double2* __restrict__ zinv,
+                                                           const double2* __restrict__ z, int nbx,
+                                                           double* __restrict__ pl) {
+  __shared__ double red[kWG / 64];
+  const int64_t n = m.n[0], j = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  const int t0 = CV ? (int)blockIdx.y : 0, t1 = CV ? t0 + 1 : m.T;
+  double s0 = 0.0, s1 = 0.0;
+  if (j < n) {
+    for (int b = 0; b < B; ++b)
+      for (int t = t0; t < t1; ++t) {
+        const double2 zv = z[((int64_t)b * m.T + t) * n + j];
+        s0 = __builtin_fma(zv.x, zv.x, __builtin_fma(zv.y, zv.y, s0));
+      }
+    for (int t = t0; t < t1; ++t) s1 += zinv[m.offk[t] + j].x;
+  }
+  s0 = block_sum(s0, red);
+  s1 = block_sum(s1, red);
+  if (threadIdx.x == 0) {
+    pl[((int64_t)t0 * kWmfLossQ + 0) * nbx + blockIdx.x] = s0;
+    pl[((int64_t)t0 * kWmfLossQ + 1) * nbx + blockIdx.x] = s1;
+  }
+}
+
+template <int FAM, bool CV>
+__global__ __launch_bounds__(kWG) void k_wide_mt_loss_grad(WmfLay m, int B, double cv_weight,
+                                                           const double2* __restrict__ zinv,
+                                                           const double2* __restrict__ z, int nbx,
+                                                           const double* __restrict__ pl, double2* __restrict__ glp) {
+  __shared__ double red[kWG / 64];
+  __shared__ double c1s[kWmfT], c2s[kWmfT];
+  const int T = m.T;
+  const int64_t n = m.n[0], j = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  const double tn = (double)T * (double)n, wn2 = cv_weight * (double)n * (double)n;
+  for (int t = 0; t < (CV ? T : 1); ++t) {
+    const double N = wmf_total(pl + ((int64_t)t * kWmfLossQ + 0) * nbx, nbx, red);
+    const double S = wmf_total(pl + ((int64_t)t * kWmfLossQ + 1) * nbx, nbx, red);
+    const WmfCoef c = wmf_loss_coef(CV, N, S, tn, wn2);
+    if (threadIdx.x == 0) c1s[t] = c.c1, c2s[t] = c.c2;
+  }
+  __syncthreads();
+  if (j >= n) return;
+  const double2* Z = zinv + j;
+  const double2* zj = z + j;
+  for (int r = 0; r < T; ++r)
+    for (int c = r; c < T; ++c) {
+      double wx = 0.0, wy = 0.0;
+      for (int t = 0; t < T; ++t) {
+        const double2 art = wmf_ainv<FAM>(m, Z, r, t), act = wmf_ainv<FAM>(m, Z, c, t);
+        double2 srt = make_double2(0.0, 0.0), stc = make_double2(0.0, 0.0);
+        for (int b = 0; b < B; ++b) {
+          const double2* zb = zj + (int64_t)b * T * n;
+          const double2 zr = zb[(int64_t)r * n], zt = zb[(int64_t)t * n], zc = zb[(int64_t)c * n];
+          srt += cmulc(zr, zt);
+          stc += cmulc(zt, zc);
+        }
+        const double2 e1 = wmf_a_mulc_a<FAM>(art, act);
+        double2 e2 = wmf_s_mulc_a<FAM>(srt, act);
+        e2 += wmf_a_mul_s<FAM>(art, stc);
+        const double c1 = c1s[CV ? t : 0], c2 = c2s[CV ? t : 0];
+        wx = __builtin_fma(-c1, e2.x, __builtin_fma(c2, e1.x, wx));
+        wy = __builtin_fma(-c1, e2.y, __builtin_fma(c2, e1.y, wy));
+      }
+      glp[m.offk[r] + (int64_t)(c - r) * n + j] = r == c ? make_double2(wx, 0.0) : make_double2(2.0 * wx, 2.0 * wy);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The step, one workgroup.  raw = [scale, dl lengthscales, noise, task factor T_all x rank, task noise T_all].
 //   mode 0  the natural scale / lengthscale row of the current raw parameters, the constant gradient rows of
 //           fgp_mt_mll_grad (gn [B] = 1/2, gl = 1/2 w) and the cleared info flag, before the first k1 of a run
@@ -170,6 +316,9 @@ struct WmfStep {
   double* nat;               // [1 + d]       natural scale, lengthscales
   double* gn;                // [B], then gl [1]
   int* info;
+  int loss;                  // FGP_LOSS_MLL / _GCV / _CV
+  double cv_weight;
+  const double* pl;          // GCV / CV: k_wide_mt_loss_sums' partials [NT][2][nbx]
 };
 
 __global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, int mode, int init) {
@@ -241,7 +390,26 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, i
       }
       grad[x] = gs;
     }
-    if (tid == 0) {
+    if (s.loss != FGP_LOSS_MLL) {
+      // GCV / CV: the second level of the loss sums in k_wide_mt_loss_grad's order; the row (loss, N, D) or
+      // (loss, NaN, NaN); tot[2 np], tot[2 np + 1], mll_const and w are unread
+      const bool cv = s.loss == FGP_LOSS_CV;
+      const double nn = (double)m.n[0], tn = (double)m.T * nn, wn2 = s.cv_weight * nn * nn;
+      double loss = 0.0, t1 = nan(""), t2 = nan("");
+      for (int t = 0; t < (cv ? m.T : 1); ++t) {
+        const double N = wmf_total(s.pl + ((int64_t)t * kWmfLossQ + 0) * s.nbx, s.nbx, red);
+        const double S = wmf_total(s.pl + ((int64_t)t * kWmfLossQ + 1) * s.nbx, s.nbx, red);
+        const WmfCoef c = wmf_loss_coef(cv, N, S, tn, wn2);
+        loss += c.loss;                                                     // the tasks in ascending order
+        if (!cv) t1 = N, t2 = c.D;
+      }
+      if (tid == 0) {
+        double* lh = f.loss_hist + (int64_t)iter * 3;
+        lh[0] = loss;
+        lh[1] = t1;
+        lh[2] = t2;
+      }
+    } else if (tid == 0) {
       double* lh = f.loss_hist + (int64_t)iter * 3;
       const double t1 = tot[2 * np], t2 = s.w * tot[2 * np + 1];
       lh[0] = 0.5 * (t1 + t2) + f.mll_const;
@@ -286,6 +454,7 @@ struct WmfPlan {
   int log2n[kWmfT];
   // byte offsets into work
   size_t o_nat, o_gn, o_info, o_dsl, o_a, o_b, o_w, o_lams, o_fac, o_zinv, o_glp, o_z, o_ld, o_part, o_pb, bytes;
+  size_t o_pl, pl_bytes;                           // GCV / CV: k_wide_mt_loss_sums' partials, after pb (MLL: empty)
 };
 
 static size_t wmf_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -321,6 +490,15 @@ static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
   }
   if (rn / m.n[T - 1] > FGP_MT_MAX_ROWS)
     return set_error(kErrUnsupported, "%s: n spread too wide (%lld block rows)", fn, (long long)(rn / m.n[T - 1]));
+  const int loss = a->loss_metric;
+  if (loss != FGP_LOSS_MLL && loss != FGP_LOSS_GCV && loss != FGP_LOSS_CV)
+    return set_error(kErrInvalid, "%s: loss_metric=%d not FGP_LOSS_MLL / _GCV / _CV", fn, loss);
+  if (loss == FGP_LOSS_CV && !std::isfinite(a->cv_weight)) return set_error(kErrInvalid, "%s: cv_weight is not finite", fn);
+  if (loss != FGP_LOSS_MLL && m.n[T - 1] != m.n[0])
+    return set_error(kErrUnsupported, "%s: loss_metric=%d needs the same n in every task (n[0]=%lld, n[%d]=%lld)", fn, loss,
+                     (long long)m.n[0], T - 1, (long long)m.n[T - 1]);
+  if (loss == FGP_LOSS_CV && T == 1)
+    return set_error(kErrUnsupported, "%s: loss_metric=FGP_LOSS_CV with T=1 (one task's inv_diag is another function)", fn);
   if (a->B < 1) return set_error(kErrInvalid, "%s: B=%d (at least one data vector)", fn, a->B);
   if (a->dl != 1 && a->dl != a->d) return set_error(kErrInvalid, "%s: dl=%d not in {1, d=%d}", fn, a->dl, a->d);
   if (a->rank < 0 || a->rank > FGP_MT_MAX_TASKS)
@@ -367,6 +545,8 @@ static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
   p.o_ld = o, o += wmf_align(8 * (size_t)m.n[T - 1]);
   p.o_part = o, o += wmf_align(8 * (np + 1) * 2 * (size_t)p.nbx);
   p.o_pb = o, o += wmf_align(8 * (1 + d) * (size_t)p.nbx);               // fgp_wide_mt_k1_bwd's partials (G = 1)
+  p.pl_bytes = loss == FGP_LOSS_MLL ? 0 : 8 * (size_t)kWmfLossQ * (loss == FGP_LOSS_CV ? (size_t)T : 1) * (size_t)p.nbx;
+  p.o_pl = o, o += wmf_align(p.pl_bytes);
   p.bytes = o;
   return kOk;
 }
@@ -378,7 +558,7 @@ enum WmfStage {
   kWmsK1,             // fgp_wide_mt_k1 of every pair
   kWmsForward,        // lambda = ft(k1), one batched call per sorted task
   kWmsLams,           // k_wide_mt_lams
-  kWmsBlocks,         // fgp_mt_factor, fgp_mt_solve, fgp_mt_selinv, fgp_mt_mll_grad
+  kWmsBlocks,         // fgp_mt_factor, fgp_mt_solve, fgp_mt_selinv, fgp_mt_mll_grad (GCV / CV: the loss sums and gradient)
   kWmsContract,       // k_wide_mt_contract
   kWmsAdjoint,        // u = the adjoint transforms of g~
   kWmsK1Bwd,          // fgp_wide_mt_k1_bwd of every pair
@@ -392,7 +572,7 @@ struct WmfCtx {
   const WmfPlan* p;
   WmfStep s;
   Switches sw;
-  double *nat, *gn, *dsl, *A, *logdet, *part, *pb;
+  double *nat, *gn, *dsl, *A, *logdet, *part, *pb, *pl;
   int* info;
   char* Bf;
   void* W;
@@ -420,6 +600,7 @@ static WmfCtx wmf_ctx(const fgp_wide_mt_fit_desc* a, const WmfPlan& p) {
   c.logdet = reinterpret_cast<double*>(w + p.o_ld);
   c.part = reinterpret_cast<double*>(w + p.o_part);
   c.pb = reinterpret_cast<double*>(w + p.o_pb);
+  c.pl = reinterpret_cast<double*>(w + p.o_pl);
   c.esz = p.lat ? 16 : 8;
   WmfStep& s = c.s;
   s.f.n_params = p.n_params;
@@ -437,9 +618,24 @@ static WmfCtx wmf_ctx(const fgp_wide_mt_fit_desc* a, const WmfPlan& p) {
   s.rg_factor = a->rg_factor, s.rg_vtask = a->rg_vtask;
   s.w = a->logdet_weight, s.lr = a->lr;
   s.part = c.part, s.dsl = c.dsl, s.nat = c.nat, s.gn = c.gn, s.info = c.info;
+  s.loss = a->loss_metric, s.cv_weight = a->cv_weight, s.pl = c.pl;
   c.sw = read_switches();
   c.y = static_cast<const double2*>(a->y);
   return c;
+}
+
+// GCV / CV: dL/dlams from the selected inverse and the solutions, in place of fgp_mt_mll_grad -- two launches, the sums'
+// reduction between them
+template <int FAM, bool CV>
+static int wmf_loss_stage(const WmfCtx& c, hipStream_t st) {
+  const fgp_wide_mt_fit_desc* a = c.a;
+  const WmfPlan& p = *c.p;
+  const dim3 gs((unsigned)p.nbx, CV ? (unsigned)p.lay.T : 1u);
+  k_wide_mt_loss_sums<CV><<<gs, kWG, 0, st>>>(p.lay, a->B, c.zinv, c.z, p.nbx, c.pl);
+  int rc = check_launch("k_wide_mt_loss_sums");
+  if (rc != kOk) return rc;
+  k_wide_mt_loss_grad<FAM, CV><<<(unsigned)p.nbx, kWG, 0, st>>>(p.lay, a->B, a->cv_weight, c.zinv, c.z, p.nbx, c.pl, c.glp);
+  return check_launch("k_wide_mt_loss_grad");
 }
 
 // Stage `stage` of iteration `iter` (the history row the step writes).  mode: the prologue's init flag, the step's mode
@@ -487,8 +683,10 @@ static int wmf_stage(const WmfCtx& c, int iter, int stage, int mode, hipStream_t
       rc = fgp_mt_factor(lay, c.lams, 1, c.fac, c.logdet, c.info, st);
       if (rc == kOk) rc = fgp_mt_solve(lay, c.fac, 1, c.y, p.rn, a->B, c.z, st);
       if (rc == kOk) rc = fgp_mt_selinv(lay, c.fac, 1, c.zinv, st);
-      if (rc == kOk) rc = fgp_mt_mll_grad(lay, c.zinv, c.z, c.gn, c.gn + a->B, a->B, 1, c.glp, st);
-      return rc;
+      if (rc != kOk) return rc;
+      if (a->loss_metric == FGP_LOSS_MLL) return fgp_mt_mll_grad(lay, c.zinv, c.z, c.gn, c.gn + a->B, a->B, 1, c.glp, st);
+      if (a->loss_metric == FGP_LOSS_CV) return p.lat ? wmf_loss_stage<0, true>(c, st) : wmf_loss_stage<1, true>(c, st);
+      return p.lat ? wmf_loss_stage<0, false>(c, st) : wmf_loss_stage<1, false>(c, st);
     case kWmsContract: {
       const dim3 gc((unsigned)p.nbx, (unsigned)np + 1);
       if (p.lat)
@@ -602,6 +800,16 @@ int fgp_wide_mt_fit_work_layout(const fgp_wide_mt_fit_desc* desc, int64_t offset
   const size_t o[15] = {p.o_nat,  p.o_gn,   p.o_info, p.o_dsl, p.o_a,  p.o_b,    p.o_w, p.o_lams,
                         p.o_fac, p.o_zinv, p.o_glp,  p.o_z,   p.o_ld, p.o_part, p.o_pb};
   for (int i = 0; i < 15; ++i) offsets[i] = (int64_t)o[i];
+  return kOk;
+}
+
+int fgp_wide_mt_fit_loss_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[2]) {
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_loss_layout", desc, p);
+  if (rc != kOk) return rc;
+  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_loss_layout: null pointer: offsets");
+  offsets[0] = (int64_t)p.o_pl;
+  offsets[1] = (int64_t)p.pl_bytes;
   return kOk;
 }
 

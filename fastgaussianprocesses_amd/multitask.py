@@ -464,6 +464,15 @@ class MultiTaskFastGP(AbstractFastGP):
             return False
         return all(self._wide_pair_spec(min(a, b), max(a, b)) is not None for a in act for b in act)
 
+    def _mt_wide_alt_ok(self):
+        """fit(loss_metric="GCV" / "CV") at 9 <= d <= 64 on the device (fgp_wide_mt_fit_desc.loss_metric): under
+        FGP_WIDE_FIT_DEVICE=1, _mt_wide_ok's domain with the same n > 0 in every task (the closed forms of T tasks of
+        equal n; unequal n keeps the generic loop)."""
+        if os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] != "1" or not ops._wide(self.d):
+            return False
+        ns = self._ns
+        return ns[0] > 0 and all(v == ns[0] for v in ns) and self._mt_wide_ok()
+
     def _mt_spectra(self, n):
         """Pair spectra Phi^{kl}_S = ft(B^{kl}_S) [T (T+1)/2, 2^d, n] (pairs k <= l row-major): with the
         derivative parts of get_k1parts(k, l) (abstract_fast_gp.py:173-180) and _kernel_from_parts'
@@ -539,9 +548,10 @@ class MultiTaskFastGP(AbstractFastGP):
     def _fused_engine(self, iterations, lr, ysq=None, d_out=None, loss_metric="MLL", cv_weight=1.0):
         """FusedMLL in multitask spectral mode (G = 1; loss_metric MLL, GCV (ABI 17) or CV (ABI 18)); the general
         engine (MtGeneralEngine, MLL) outside its domain (_mt_fused_ok: equal n, fixed task kernel); at 9 <= d <= 64
-        the wide engine (WideMtEngine, MLL)."""
+        the wide engine (WideMtEngine: MLL, or GCV / CV with equal n)."""
         if ops._wide(self.d):
-            return WideMtEngine(self, lr, min(iterations + 1, 64))       # (_device_fit_args: MLL inside _mt_wide_ok)
+            # (_device_fit_args: inside _mt_wide_ok, GCV / CV inside _mt_wide_alt_ok)
+            return WideMtEngine(self, lr, min(iterations + 1, 64), loss_metric=loss_metric, cv_weight=cv_weight)
         learn = loss_metric != "MLL" and not self._mt_fused_ok() and self._mt_learn_ok()
         if not self._mt_fused_ok() and not learn:
             return MtGeneralEngine(self, lr, min(iterations + 1, 64))
@@ -886,7 +896,8 @@ class MultiTaskFastGP(AbstractFastGP):
         """The MLL on the device inside _mt_fused_ok or _mt_general_ok, or inside _mt_wide_ok under
         FGP_WIDE_FIT_DEVICE=1; GCV / CV of T tasks with equal n and a fixed or
         a learned task kernel (k_mt_spec_iter's GCV / CV variants + k_spec_loss_step, ABI 17 / 18; util.py:371-394,
-        abstract_gp.py:242-272) unless FGP_ALT_LOSS_DEVICE=0."""
+        abstract_gp.py:242-272), or at 9 <= d <= 64 inside _mt_wide_alt_ok (fgp_wide_mt_fit_desc.loss_metric), unless
+        FGP_ALT_LOSS_DEVICE=0."""
         if optimizer is not None or masks is not None:
             return None
         if loss_metric == "MLL":
@@ -895,7 +906,8 @@ class MultiTaskFastGP(AbstractFastGP):
             # 9 <= d <= 64: opt-in, the switch of a single wide GP's fit (default: the generic autograd loop)
             wide = os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1" and self._mt_wide_ok()
             return {} if wide else None
-        ok = (self._mt_fused_ok() or self._mt_learn_ok()) and os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
+        ok = (self._mt_fused_ok() or self._mt_learn_ok() or self._mt_wide_alt_ok()) and \
+            os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
         if loss_metric == "CV":
             # (one task: the reference's inv_diag is the single-task formula without the noise, util.py:383-386; a
             # per-point cv_weights needs the points' coefficients, not their Parseval sum)
@@ -1356,12 +1368,17 @@ class MtGeneralEngine(FitEngine):
 
 
 class WideMtEngine(MtGeneralEngine):
-    """Device-resident MLL fit of a multitask / derivative-informed GP at 9 <= d <= 64 (include/fgp_hip.h, an addition
+    """Device-resident fit of a multitask / derivative-informed GP at 9 <= d <= 64 (include/fgp_hip.h, an addition
     to ABI 20: fgp_wide_mt_fit_run): MtGeneralEngine's raw vector, histories and task-kernel hooks, with the pair
     spectra (which do not exist at these d) replaced by every sorted pair's dimension-major first-column parts and its
-    fused spec; lambda is transformed from k1 in every iteration."""
+    fused spec; lambda is transformed from k1 in every iteration.  loss_metric "MLL", or "GCV" /
+    "CV" for tasks of equal n (cv_weight: CV's scalar weight); their loss_hist rows are (loss, N, D) and
+    (loss, NaN, NaN)."""
 
-    def __init__(self, gp, lr, max_iters):
+    def __init__(self, gp, lr, max_iters, loss_metric="MLL", cv_weight=1.0):
+        if loss_metric not in ("MLL", "GCV", "CV"):
+            raise ValueError("loss_metric must be MLL, GCV or CV")
+        self.loss_metric = loss_metric
         self.gp = gp
         self.device = dev = gp.device
         lo = _Layout(gp._ns)
@@ -1415,6 +1432,8 @@ class WideMtEngine(MtGeneralEngine):
         # 1/2 (norm + w logdet) + 1/2 d_out sum(n) log(2 pi)
         desc.logdet_weight = float(d_out)
         desc.mll_const = 0.5 * float(mll_constant(d_out, sum(gp._ns)))
+        desc.loss_metric = {"MLL": N.LOSS_MLL, "GCV": N.LOSS_GCV, "CV": N.LOSS_CV}[loss_metric]
+        desc.cv_weight = float(cv_weight)
         wb = ctypes.c_int64(0)
         N.call("fgp_wide_mt_fit_work", desc, ctypes.byref(wb))
         self.work = torch.empty((max(1, wb.value),), dtype=torch.uint8, device=dev)

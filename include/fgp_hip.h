@@ -896,7 +896,17 @@ int fgp_mt_fit_run(const fgp_mt_fit_desc* desc, int iter0, int iters, int final_
  *        noise exp (vtask_exp = 1) or identity (0).  n_params = 2 + dl + T_all rank + T_all.
  * loss_hist [iters][3] = (loss, sum_b norm_b, w logdet); raw_hist [iters][n_params]; row i of both holds the loss and
  * the parameters AT iteration i, before its step.  grad_out [n_params]: the raw gradient of the last evaluation.
- * iter0, iters, final_no_update and lr as fgp_wide_fit_run.  y and work must be 16-byte aligned. */
+ * iter0, iters, final_no_update and lr as fgp_wide_fit_run.  y and work must be 16-byte aligned.
+ * loss_metric FGP_LOSS_GCV / FGP_LOSS_CV (AbstractGP.fit's alternative losses, abstract_gp.py:242-273 over util.py:371-394),
+ * for tasks of EQUAL n, where every frequency class has one row per task and the selected inverse is the dense
+ * A_j = Lambda_j^-1: GCV = N / D, N = sum_b sum_j |z_bj|^2, D = (sum_j Re tr A_j / (T n))^2; CV = cv_weight sum_t N_t / I_t^2,
+ * N_t = sum_b sum_j |z_bjt|^2, I_t = sum_j Re A_j[t, t] / n (the noise included: the reference's num_tasks > 1 branch).
+ * fgp_mt_mll_grad is replaced by two kernels with the sums' reduction between them (per-workgroup partials, then
+ * dL/dlams in fgp_mt_mll_grad's convention and layout), so an iteration is 3 np + 2 T + 8 calls; everything after it
+ * runs unchanged.  loss_hist rows are (loss, N, D) under GCV and (loss, NaN, NaN) under CV; logdet_weight and
+ * mll_const are unread.  Refused before any HIP call: loss_metric outside the three and a non-finite cv_weight under
+ * FGP_LOSS_CV (FGP_ERR_INVALID), GCV / CV with unequal n and FGP_LOSS_CV with T = 1 (FGP_ERR_UNSUPPORTED: one task's
+ * inv_diag is the formula without the noise, util.py:383-386). */
 #define FGP_WIDE_MT_FIT_PAIRS (FGP_MT_MAX_TASKS * (FGP_MT_MAX_TASKS + 1) / 2)
 typedef struct fgp_wide_mt_pair {
   const double* parts;        /* device [P][d][n_k] dimension-major parts (fgp_wide_mt_parts) of sorted pair (k, l) */
@@ -927,6 +937,8 @@ typedef struct fgp_wide_mt_fit_desc {
   double* raw_hist;
   double* grad_out;
   void* work;                         /* fgp_wide_mt_fit_work bytes */
+  int loss_metric;                    /* FGP_LOSS_MLL (0: a zeroed field is the MLL) / FGP_LOSS_GCV / FGP_LOSS_CV */
+  double cv_weight;                   /* FGP_LOSS_CV: the scalar cv_weights of AbstractGP.fit; otherwise unread */
 } fgp_wide_mt_fit_desc;
 
 /* Bytes of `work`.  Validates the desc's sizes (not its pointers) as fgp_wide_mt_fit_run does. */
@@ -953,6 +965,12 @@ extern int (fgp_wide_mt_fit_run)(const fgp_wide_mt_fit_desc* desc, int iter0, in
  * Validation as fgp_wide_mt_fit_run's, and of stage / mode / iter, before any HIP call (FGP_ERR_INVALID). */
 extern int (fgp_wide_mt_fit_work_layout)(const fgp_wide_mt_fit_desc* desc, int64_t offsets[15]);
 extern int (fgp_wide_mt_fit_stage)(const fgp_wide_mt_fit_desc* desc, int iter, int stage, int mode, void* stream);
+/* Addition to ABI 20 -- test hook, read-only, no HIP call: offsets[0] = the BYTE offset into `work` of the GCV / CV
+ * partials pl [NT][2][nbx] float64 ((N, Tr) with NT = 1 under GCV; (N_t, n I_t) per sorted task, NT = T, under CV;
+ * nbx = ceil(n / 256)), offsets[1] = their length in bytes (0 for an MLL desc).  They follow pb: offsets[0] + offsets[1]
+ * rounded up to 256 = fgp_wide_mt_fit_work's bytes, and an MLL desc's bytes and 15 offsets are what they were.  Under
+ * GCV / CV stage 4 of fgp_wide_mt_fit_stage is factor, solve, selected inverse, sums, gradient. */
+extern int (fgp_wide_mt_fit_loss_layout)(const fgp_wide_mt_fit_desc* desc, int64_t offsets[2]);
 
 /* ABI 15 -- consistency check of the fused spectral fit's last-arriver hand-off (a test hook, no reference
  * counterpart).  enable != 0 arms it for the following fgp_fit_run calls: every wave of the one-launch

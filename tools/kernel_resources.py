@@ -4,7 +4,7 @@ AMDGPU metadata notes (what the loader allocates), not from a compiler remark.
     python tools/kernel_resources.py [--lib fastgaussianprocesses_amd/_lib/libfgp_hip.so] [--grep k_fwd_cols_r2c]
 
 Copies the .so to a temporary directory, unbundles it there (llvm-objdump --offloading), and prints
-for every kernel: arch VGPRs, AGPRs, SGPRs, spills, group (LDS) segment bytes, and the waves per SIMD
+for every kernel: arch VGPRs, AGPRs, SGPRs, spills, group (LDS) and private (scratch) segment bytes, and the waves per SIMD
 that the registers allow (MI355X_MICROARCH.md 'Register files': allocation granule 8, 512 per lane).
 """
 import argparse
@@ -69,16 +69,18 @@ def main():
     ks = read_kernels(a.lib)
     names = sorted(ks)
     dem = demangle(names)
-    print("%-70s %5s %5s %5s %6s %6s %7s %5s" % ("kernel", "vgpr", "agpr", "sgpr", "vspill", "sspill", "lds", "w/simd"))
+    print("%-70s %5s %5s %5s %6s %6s %7s %7s %5s" % ("kernel", "vgpr", "agpr", "sgpr", "vspill", "sspill", "lds", "scratch",
+                                                      "w/simd"))
     for mangled, nice in zip(names, dem):
         if a.grep and not re.search(a.grep, nice):
             continue
         k = ks[mangled]
         short = nice.split("(")[0].replace("void ", "")
-        print("%-70s %5d %5d %5d %6d %6d %7d %5d" % (short[:70], k.get("vgpr_count", 0), k.get("agpr_count", 0),
-                                                   k.get("sgpr_count", 0), k.get("vgpr_spill_count", 0),
-                                                   k.get("sgpr_spill_count", 0), k.get("group_segment_fixed_size", 0),
-                                                   waves_per_simd(k.get("vgpr_count", 0), k.get("agpr_count", 0))))
+        print("%-70s %5d %5d %5d %6d %6d %7d %7d %5d" % (short[:70], k.get("vgpr_count", 0), k.get("agpr_count", 0),
+                                                       k.get("sgpr_count", 0), k.get("vgpr_spill_count", 0),
+                                                       k.get("sgpr_spill_count", 0), k.get("group_segment_fixed_size", 0),
+                                                       k.get("private_segment_fixed_size", 0),
+                                                       waves_per_simd(k.get("vgpr_count", 0), k.get("agpr_count", 0))))
 
 
 if __name__ == "__main__":

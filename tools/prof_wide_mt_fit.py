@@ -1,19 +1,25 @@
 """ms per fit iteration of a multitask / derivative-informed GP on wide inputs: the device-resident loop
 (fgp_wide_mt_fit_run, FGP_WIDE_FIT_DEVICE=1) against the generic autograd loop (the default path), in one process.
 
-    python tools/prof_wide_mt_fit.py [--iters K] [--rounds R] [--out FILE.json] [config names...]
+    python tools/prof_wide_mt_fit.py [--metric MLL|GCV|CV] [--iters K] [--rounds R] [--out FILE.json] [config names...]
 
 Each round times K iterations of the device loop and K of the generic loop, alternating, each window ending in a device
 synchronise; the figure is the median over the rounds (the spread is printed beside it).  One untimed round warms up
 every shape.  The generic iteration is AbstractFastGP._fit_generic's body (caches dropped, _loss_generic, the loss read
 back for the stopping rule, backward, torch.optim.Rprop.step).  Launch counts: the device loop's entry-point calls per
-iteration are 3 T (T + 1) / 2 + 2 T + 7 by construction; the generic loop's are the native entry points Python calls
-per iteration (counted by a spy on _native.call in a separate untimed iteration) -- its torch glue kernels come on top
-and are not counted.  Needs a GPU: there is no CPU fallback.
+iteration are 3 T (T + 1) / 2 + 2 T + 7 by construction (one more under GCV / CV); the generic loop's are the native
+entry points Python calls per iteration (counted by a spy on _native.call in a separate untimed iteration) -- its torch
+glue kernels come on top and are not counted.  Needs a GPU: there is no CPU fallback.
 
-Configurations:
+--metric GCV / CV times fit(loss_metric=...) (CV with the scalar weight 0.75).  The generic CV loss of several tasks
+solves the identity of size sum(n) (util.py:387-393): (sum n)^2 complex128 values per temporary.  Where eight of them do
+not fit the device's free memory the generic loop is not attempted and the row says so (generic_ms_per_iter = null,
+generic_skipped = the reason); the device loop is measured all the same.
+
+Configurations (mt_T<T>_d<d>_n<n>: any power-of-two n):
   mt_T3_d16_n65536     lattice, T = 3 tasks, n = 2^16 each, d = 16
   mt_T3_d64_n65536     the same, d = 64
+  mt_T3_d16_n4096      T = 3, n = 2^12, d = 16: the largest of these at which the generic CV loop runs
   deriv_T5_d16_n16384  lattice, f and four first partial derivatives, n = 2^14 each, d = 16
 """
 import argparse
@@ -39,7 +45,7 @@ def _smooth(x):
 def make_gp(name):
     if name.startswith("mt_T3"):
         d = 64 if "d64" in name else 16
-        T, n = 3, 1 << 16
+        T, n = 3, int(name.rsplit("_n", 1)[1])
         seqs = [F.Lattice(d, seed=3 + l) for l in range(T)]
         gp = F.FastGPLattice(seqs, num_tasks=T, alpha=2, device=DEV, lengthscales=0.05)
         xs = gp.get_x_next(n=[n] * T)
@@ -61,9 +67,12 @@ def make_gp(name):
     return gp
 
 
-def generic_iteration(gp, opt):
+CV_WEIGHT = 0.75
+
+
+def generic_iteration(gp, opt, metric="MLL"):
     gp._cache = {k: v for k, v in gp._cache.items() if not k[2]}
-    loss = gp._loss_generic("MLL", None, 1, 1)[0]
+    loss = gp._loss_generic(metric, None, CV_WEIGHT if metric == "CV" else 1, 1)[0]
     lv = loss.item()
     loss.backward()
     opt.step()
@@ -79,12 +88,29 @@ def window(fn, k):
     return (time.perf_counter() - t0) * 1e3 / k
 
 
-def measure(name, iters, rounds):
+def generic_skipped(gp, metric):
+    """Why the generic loop is not attempted, or None."""
+    if metric != "CV" or gp.num_tasks == 1:
+        return None
+    need = 8 * 16 * sum(gp._ns) ** 2
+    free = torch.cuda.mem_get_info()[0]
+    if need > free:
+        return "the generic CV loss solves the identity of size sum(n) = %d: about %.0f GB, %.0f GB free" % (
+            sum(gp._ns), need / 1e9, free / 1e9)
+    return None
+
+
+def measure(name, iters, rounds, metric="MLL"):
     os.environ["FGP_WIDE_FIT_DEVICE"] = "1"
     gp_dev, gp_gen = make_gp(name), make_gp(name)
     assert gp_dev._mt_wide_ok(), name
-    eng = gp_dev._fused_engine(iters, 0.1)
+    if metric == "MLL":
+        eng = gp_dev._fused_engine(iters, 0.1)
+    else:
+        assert gp_dev._device_fit_args(metric, None, None, CV_WEIGHT) is not None, (name, metric)
+        eng = gp_dev._fused_engine(iters, 0.1, loss_metric=metric, cv_weight=CV_WEIGHT)
     assert type(eng).__name__ == "WideMtEngine"
+    skipped = generic_skipped(gp_gen, metric)
     opt = gp_gen.get_default_optimizer(None)
     T = eng.lo.T
     raw0 = eng.raw.clone()
@@ -92,7 +118,8 @@ def measure(name, iters, rounds):
     spy, real = [], N.call
     N.call = lambda nm, *a: (spy.append(nm), real(nm, *a))[1]
     try:
-        generic_iteration(gp_gen, opt)                      # (also the generic loop's first warm-up iteration)
+        if skipped is None:
+            generic_iteration(gp_gen, opt, metric)          # (also the generic loop's first warm-up iteration)
     finally:
         N.call = real
 
@@ -102,7 +129,7 @@ def measure(name, iters, rounds):
     def gen_k(k):
         o = gp_gen.get_default_optimizer(None)
         for _ in range(k):
-            generic_iteration(gp_gen, o)
+            generic_iteration(gp_gen, o, metric)
 
     def reset():
         """Every window starts from the initial parameters (both loops then walk the same trajectory)."""
@@ -115,16 +142,20 @@ def measure(name, iters, rounds):
     for r in range(rounds + 1):                             # round 0: warm-up of every shape of the timed windows
         reset()
         td = window(dev_k, iters)
-        tg = window(gen_k, iters)
+        tg = window(gen_k, iters) if skipped is None else None
         if r > 0:
             dev.append(td)
             gen.append(tg)
-    return dict(config=name, d=gp_dev.d, ns=list(gp_dev._ns), iters=iters, rounds=rounds,
-                device_ms_per_iter=statistics.median(dev), device_ms_min_max=[min(dev), max(dev)],
-                generic_ms_per_iter=statistics.median(gen), generic_ms_min_max=[min(gen), max(gen)],
-                ratio_generic_over_device=statistics.median(gen) / statistics.median(dev),
-                device_entry_point_calls_per_iter=3 * (T * (T + 1) // 2) + 2 * T + 7,
-                generic_native_calls_per_iter=len(spy))
+    row = dict(config=name, metric=metric, d=gp_dev.d, ns=list(gp_dev._ns), iters=iters, rounds=rounds,
+               device_ms_per_iter=statistics.median(dev), device_ms_min_max=[min(dev), max(dev)],
+               device_entry_point_calls_per_iter=3 * (T * (T + 1) // 2) + 2 * T + 7 + (metric != "MLL"))
+    if skipped is None:
+        row.update(generic_ms_per_iter=statistics.median(gen), generic_ms_min_max=[min(gen), max(gen)],
+                   ratio_generic_over_device=statistics.median(gen) / statistics.median(dev),
+                   generic_native_calls_per_iter=len(spy))
+    else:
+        row.update(generic_ms_per_iter=None, generic_skipped=skipped)
+    return row
 
 
 def main():
@@ -132,14 +163,19 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--metric", default="MLL", choices=["MLL", "GCV", "CV"])
+    ap.add_argument("--append", action="store_true", help="keep the rows --out already holds")
     ap.add_argument("configs", nargs="*", default=["mt_T3_d16_n65536", "mt_T3_d64_n65536", "deriv_T5_d16_n16384"])
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("prof_wide_mt_fit: no GPU; nothing is measured without one")
     torch.set_default_dtype(torch.float64)
     rows = []
+    if a.append and a.out and os.path.isfile(a.out):
+        with open(a.out) as f:
+            rows = json.load(f)
     for name in a.configs:
-        rows.append(measure(name, a.iters, a.rounds))
+        rows.append(measure(name, a.iters, a.rounds, a.metric))
         print(json.dumps(rows[-1]), flush=True)
         if a.out:
             with open(a.out, "w") as f:
