@@ -249,6 +249,13 @@ _SIGNATURES = {
     "fgp_mt_wide_post_mean": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_pd, _c_pi, _c_pd,
                               _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_vp, _c_i64,
                               _c_vp],
+    # addition to ABI 20: the task-pair kernel rows and the matrix-free posterior mean at d <= MAX_D
+    "fgp_mt_rows": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_int, _c_pi, _c_pd, _c_pd, _c_pi, _c_pd,
+                    _c_int, _c_vp, _c_int, _c_vp, _c_vp],
+    "fgp_mt_post_mean_work": [_c_i64, _c_i64, _c_int, _c_i64, _c_pl],
+    "fgp_mt_post_mean": [_c_int, _c_vp, _c_i64, _c_vp, _c_i64, _c_int, _c_int, _c_pi, _c_pd, _c_pd, _c_pi, _c_pd,
+                         _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_int, _c_vp, _c_int, _c_vp, _c_i64, _c_vp, _c_i64,
+                         _c_vp],
     # addition to ABI 20: the device-resident fit loop of wide multitask / derivative-informed GPs
     "fgp_wide_mt_fit_work": [_P_WIDEMTFIT, _c_pl],
     "fgp_wide_mt_fit_run": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],

@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(HERE, "_lib")
 LIB = os.path.join(LIB_DIR, "libfgp_hip.so")
 OBJ_DIR = os.path.join(LIB_DIR, "obj")
 SOURCES = ["fgp_runtime.hip", "fgp_transforms.hip", "fgp_nll.hip", "fgp_nll_re.hip", "fgp_predict.hip", "fgp_multitask.hip", "fgp_points.hip",
-           "fgp_spectral.hip", "fgp_wide.hip", "fgp_wide_fit.hip", "fgp_wide_mt.hip", "fgp_wide_mt_fit.hip"]
+           "fgp_spectral.hip", "fgp_wide.hip", "fgp_wide_fit.hip", "fgp_wide_mt.hip", "fgp_wide_mt_fit.hip", "fgp_mt_pred.hip"]
 HEADERS = ["fgp_common.h", "fgp_runtime.h", "fgp_nll.h", "fgp_factors.h", "fgp_wide.h"]
 # gfx950 (MI355X) only: the kernels' inter-workgroup hand-offs rely on gfx9 store counting (csrc/fgp_spectral.hip
 # refuses to compile for other families)

@@ -54,4 +54,20 @@ __device__ __forceinline__ unsigned long long to_bits(double v, int tbits) {
   return (unsigned long long)(long long)floor(r * ldexp(1.0, tbits));
 }
 
+// One derivative part of the task-pair kernel (k_mt_parts' arithmetic): coef B_order(dl) for lattices (dl = (x - z)
+// mod 1), coef (add + omega_order(dv)) for nets (dv = x XOR z as t-bit integers).  Shared by the wide (fgp_wide_mt.hip)
+// and the d <= 8 (fgp_mt_pred.hip) kernels; wmt_base / wmt_finish are its two steps, for a kernel that fetches coef and
+// add only after the polynomial.
+__device__ __forceinline__ double wmt_base(int fam, int order, double dl, unsigned long long dv, int t) {
+  if (fam == 0) return bernoulli_any(order, dl);
+  return order == 1 ? walsh1(dv, t) : walsh_omega(order, dv, t);
+}
+__device__ __forceinline__ double wmt_finish(int fam, double coef, double add, double base) {
+  return fam == 0 ? coef * base : coef * (add + base);
+}
+__device__ __forceinline__ double wmt_part(int fam, int order, double coef, double add, double dl,
+                                           unsigned long long dv, int t) {
+  return wmt_finish(fam, coef, add, wmt_base(fam, order, dl, dv, t));
+}
+
 }  // namespace fgp

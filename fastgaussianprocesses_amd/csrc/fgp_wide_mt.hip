@@ -53,12 +53,7 @@ struct MtCc {
   double cc[kMtP];
 };
 
-__device__ __forceinline__ double wmt_part(int fam, int order, double coef, double add, double dl,
-                                           unsigned long long dv, int t) {
-  if (fam == 0) return coef * bernoulli_any(order, dl);
-  const double om = order == 1 ? walsh1(dv, t) : walsh_omega(order, dv, t);
-  return coef * (add + om);
-}
+// (wmt_part, one derivative part from the coordinate difference: fgp_factors.h)
 
 // ------------------------------------------------------------------------------------------------ parts
 // thread = pair e; the tables in LDS; parts[(p d + j) E + e]: a wave's store of one (p, j) is contiguous

@@ -7,7 +7,8 @@ predictions; abstract_fast_gp.py:29-31,155-191 task-pair caches and derivative k
 40-62, 95-183, 275-394 caches and the block inverse).
 
 Where the work runs:
-  * derivative kernel parts, per task pair and for prediction rows  -> fgp_mt_parts (HIP)
+  * derivative kernel parts, per task pair                         -> fgp_mt_parts (HIP)
+  * prediction rows and the matrix-free posterior mean, d <= 8      -> fgp_mt_rows / fgp_mt_post_mean (HIP)
   * at 9 <= d <= 64: dimension-major parts, the fused first column of a task pair and its
     adjoint, kernel rows from the points                              -> fgp_wide_mt_parts / _k1 / _k1_bwd / _rows
   * ft / ift of every task's data and first-column kernels           -> fgp_fftbr / fgp_ifftbr / fgp_fwht
@@ -578,12 +579,13 @@ class MultiTaskFastGP(AbstractFastGP):
         c0, c1 = self.derivatives_coeffs[ta], self.derivatives_coeffs[tb]
         bd0, bd1 = self.derivatives[ta], self.derivatives[tb]
         N = x.shape[0]
-        spec = self._wide_pair_spec(ta, tb)
+        spec = self._fused_pair_spec(ta, tb)
         if spec is not None and not self._gradmode() and N > 0 and z.shape[0] > 0 and torch.is_floating_point(x):
-            # d > 8 without an autograd graph: the kernel rows from the points (fgp_wide_mt_rows), no parts array
+            # without an autograd graph: the kernel rows from the points (fgp_mt_rows at d <= 8, fgp_wide_mt_rows above),
+            # no parts array
             xc = x.to(device=self.device, dtype=torch.float64)
             assert bool(((0 <= xc) & (xc <= 1)).all()), "x should have all elements in [0,1]"
-            rows = ops.wide_mt_rows(spec, xc, z_dn if z_dn is not None else self._kargs(z).T.contiguous(),
+            rows = ops.mt_pair_rows(spec, xc, z_dn if z_dn is not None else self._kargs(z).T.contiguous(),
                                     self._wide_hyp_rows(), zip_pairs)
             return rows.reshape(self._wide_param_rows() + rows.shape[1:])
         per = max(1, (1 if zip_pairs else z.shape[0]) * len(b0) * len(b1) * self.d)
@@ -600,11 +602,17 @@ class MultiTaskFastGP(AbstractFastGP):
                                            bd0, bd1, c0, c1)
         return torch.cat(outs, -1 if zip_pairs else -2)
 
-    # ------------------------------------------------------------------ wide inputs (d > 8)
+    # ------------------------------------------------------------------ fused task-pair kernels
     def _wide_pair_spec(self, ta, tb):
-        """ops.WideMtSpec of the task pair when its kernel takes the fused wide entry points (d > 8, at most 16
-        derivative multi-index pairs, FGP_WIDE_FUSED not 0), else None: the torch formulation over the parts."""
-        if not ops._wide(self.d) or not ops.wide_fused():
+        """_fused_pair_spec at d > 8, None at d <= 8: the spec of what only the wide entry points do (the first column
+        of get_lam, the device-resident fit)."""
+        return self._fused_pair_spec(ta, tb) if ops._wide(self.d) else None
+
+    def _fused_pair_spec(self, ta, tb):
+        """ops.WideMtSpec of the task pair when its prediction rows take the fused entry points -- at most 16 derivative
+        multi-index pairs, and FGP_MT_FUSED_ROWS not 0 at d <= 8 (fgp_mt_rows / fgp_mt_post_mean), FGP_WIDE_FUSED not 0
+        above (fgp_wide_mt_*) --, else None: the torch formulation over the parts."""
+        if not ops.mt_pair_fused(self.d):
             return None
         memo = self.__dict__.setdefault("_wide_pair_specs", {})
         if (ta, tb) not in memo:
@@ -618,7 +626,7 @@ class MultiTaskFastGP(AbstractFastGP):
         return tuple(torch.broadcast_shapes(self.scale.shape[:-1], self.lengthscales.shape[:-1]))
 
     def _wide_hyp_rows(self):
-        """[G, 1 + d] (scale, lengthscales) over _wide_param_rows, for fgp_wide_mt_rows."""
+        """[G, 1 + d] (scale, lengthscales) over _wide_param_rows, for fgp_mt_rows / fgp_wide_mt_rows."""
         rows = self._wide_param_rows()
         s, ls = self.scale.detach(), self.lengthscales.detach()
         return torch.cat([s.expand(rows + (1,)).reshape(-1, 1), ls.expand(rows + (self.d,)).reshape(-1, self.d)], -1)
@@ -644,8 +652,8 @@ class MultiTaskFastGP(AbstractFastGP):
         return parts
 
     def _xb_dm(self, task, n):
-        """Task's first n points dimension-major [d, n] (float64 lattice / int64 net), as fgp_wide_mt_rows takes the
-        training points; cached per (task, n)."""
+        """Task's first n points dimension-major [d, n] (float64 lattice / int64 net), as fgp_mt_rows and
+        fgp_wide_mt_rows take the training points; cached per (task, n)."""
         memo = self.__dict__.setdefault("_xb_dm_cache", {})
         if (task, n) not in memo:
             memo[task, n] = self.get_xb(task, n).T.contiguous()
@@ -934,7 +942,7 @@ class MultiTaskFastGP(AbstractFastGP):
         for t in tasks:
             blocks = []
             for l in range(self.num_tasks):
-                z_dn = self._xb_dm(l, ns[l]) if self._wide_pair_spec(t, l) is not None and ns[l] > 0 else None
+                z_dn = self._xb_dm(l, ns[l]) if self._fused_pair_spec(t, l) is not None and ns[l] > 0 else None
                 kb = self._kmat_block(x, self.get_xb(l, ns[l]), t, l, z_dn=z_dn)
                 blocks.append(Kt[..., t, l, None, None] * kb)
             bshape = torch.broadcast_shapes(*[b.shape[:-2] for b in blocks])
@@ -950,9 +958,9 @@ class MultiTaskFastGP(AbstractFastGP):
 
     def _post_mean_mf(self, x, tasks):
         """m[..., a, t] = sum_l Kt[..., a, l] sum_i K_{a,l}(x_t, xb_{l,i}) coeffs[..., off_l + i] -> [*batch, T', N]
-        without a kernel row (fgp_mt_wide_post_mean, d > 8 and fused specs): one call per (requested task, task with
-        points), accumulated in ascending l; the batch flattened to B rows, the hyper-parameter rows expanded to B when
-        they are more than one and fewer than B."""
+        without a kernel row (fgp_mt_post_mean at d <= 8, fgp_mt_wide_post_mean above; fused specs): one call per
+        (requested task, task with points), accumulated in ascending l; the batch flattened to B rows, the
+        hyper-parameter rows expanded to B when they are more than one and fewer than B."""
         ns = self._ns
         xc = x.to(device=self.device, dtype=torch.float64)
         assert bool(((0 <= xc) & (xc <= 1)).all()), "x should have all elements in [0,1]"
@@ -973,7 +981,7 @@ class MultiTaskFastGP(AbstractFastGP):
                 if ns[l] == 0:
                     continue
                 w = Kt[..., a, l].expand(bshape).reshape(B)
-                ops.mt_wide_post_mean(self._wide_pair_spec(a, l), xc, self._xb_dm(l, ns[l]), hyp,
+                ops.mt_pair_post_mean(self._fused_pair_spec(a, l), xc, self._xb_dm(l, ns[l]), hyp,
                                       coeffs[:, int(off[l]):int(off[l + 1])], w, out[:, ai, :], beta)
                 beta = 1
             if beta == 0:
@@ -981,17 +989,17 @@ class MultiTaskFastGP(AbstractFastGP):
         return out.reshape(bshape + (len(tasks), Nt))
 
     def post_mean(self, x, task=None, eval=True):
-        """abstract_gp.py:352-380.  At d > 8, without an autograd graph and with a fused spec for every (requested
-        task, task) pair: the matrix-free sum of _post_mean_mf when the kernel rows [*, T', N, sum n] would exceed 2^22
-        bytes (ops.mt_wide_post_mean_route; FGP_WIDE_MT_POST_MEAN=1 / 0 forces either route), else the rows and an
-        einsum."""
+        """abstract_gp.py:352-380.  Without an autograd graph and with a fused spec for every (requested task, task)
+        pair (_fused_pair_spec: any d <= 64): the matrix-free sum of _post_mean_mf when the kernel rows [*, T', N,
+        sum n] would exceed 2^22 bytes (ops.mt_wide_post_mean_route; FGP_WIDE_MT_POST_MEAN=1 / 0 forces either route),
+        else the rows and an einsum."""
         with (torch.no_grad() if eval else torch.enable_grad() if torch.is_grad_enabled() else torch.no_grad()):
             coeffs = self.coeffs
             assert x.ndim == 2 and x.size(1) == self.d, "x must a torch.Tensor with shape (-1,d)"
             inttask, tasks = self._task_list(task)
             x = x.to(self.device)
-            if ops._wide(self.d) and not self._gradmode() and x.shape[0] > 0 and torch.is_floating_point(x) and all(
-                    self._wide_pair_spec(a, l) is not None for a in tasks for l in range(self.num_tasks)):
+            if not self._gradmode() and x.shape[0] > 0 and torch.is_floating_point(x) and all(
+                    self._fused_pair_spec(a, l) is not None for a in tasks for l in range(self.num_tasks)):
                 B = int(np.prod(self._post_mean_batch()))
                 mf = ops.mt_wide_post_mean_route(8 * B * len(tasks) * x.shape[0] * sum(self._ns))
             else:

@@ -432,6 +432,18 @@ def wide_fused():
     return os.environ.get("FGP_WIDE_FUSED", "1")[:1] != "0"
 
 
+def mt_fused_rows():
+    """FGP_MT_FUSED_ROWS=0 keeps fgp_mt_parts and the torch formulation (_kernel_from_parts) for the prediction rows of
+    multitask / derivative-informed GPs at d <= 8 (A/B runs, tests); default: fgp_mt_rows / fgp_mt_post_mean."""
+    return os.environ.get("FGP_MT_FUSED_ROWS", "1")[:1] != "0"
+
+
+def mt_pair_fused(d):
+    """The task-pair kernel of a d-dimensional GP takes the fused entry points: fgp_mt_* at d <= 8 (mt_fused_rows),
+    fgp_wide_mt_* above (wide_fused)."""
+    return wide_fused() if _wide(d) else mt_fused_rows()
+
+
 def wide_k1_raw(parts, scale_rows, ls_rows):
     """k1[g, i] = scale_rows[g] prod_j (1 + ls_rows[g, j] parts[j, i]) -> [G, n] (fgp_wide_k1); parts [d, n], d > 8."""
     require_device(parts, "wide_k1")
@@ -852,11 +864,11 @@ def wide_mt_k1(spec, parts, scale_rows, ls_rows):
     return wide_mt_k1_raw(spec, parts, scale_rows, ls_rows)
 
 
-def wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs=False):
+def wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs=False, entry="fgp_wide_mt_rows"):
     """rows[g, t, i] = K_ab(xt[t], z[:, i]) -> [Gk, N, n], or with zip_pairs (N == n) rows[g, t] = K_ab(xt[t], z[:, t])
     -> [Gk, N] (fgp_wide_mt_rows): xt [N, d] float64 test points, z_dn [d, n] dimension-major (float64 lattice / int64
     net), hyp [Gk, 1 + d] (scale, lengthscales)."""
-    require_device(xt, "wide_mt_rows")
+    require_device(xt, entry[4:])
     xt = xt.to(torch.float64).contiguous()
     Nt, d = xt.shape
     n = z_dn.shape[1]
@@ -869,42 +881,54 @@ def wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs=False):
     if zip_pairs:
         assert Nt == n
         rows = torch.empty((Gk, Nt), dtype=torch.float64, device=xt.device)
-        N.call("fgp_wide_mt_rows", spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, 1, *args, N.ptr(rows), _stream(xt))
+        N.call(entry, spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, 1, *args, N.ptr(rows), _stream(xt))
         return rows
     rows = torch.empty((Gk, Nt, n), dtype=torch.float64, device=xt.device)
     for t0 in range(0, Nt, 65535):
         t1 = min(Nt, t0 + 65535)
         sub = torch.empty((Gk, t1 - t0, n), dtype=torch.float64, device=xt.device) if Nt > 65535 else rows
-        N.call("fgp_wide_mt_rows", spec.family, N.ptr(xt[t0:t1]), t1 - t0, N.ptr(z_dn), n, 0, *args, N.ptr(sub), _stream(xt))
+        N.call(entry, spec.family, N.ptr(xt[t0:t1]), t1 - t0, N.ptr(z_dn), n, 0, *args, N.ptr(sub), _stream(xt))
         if sub is not rows:
             rows[:, t0:t1] = sub
     return rows
+
+
+def mt_rows(spec, xt, z_dn, hyp, zip_pairs=False):
+    """wide_mt_rows for d <= 8 (fgp_mt_rows): the same arguments and result."""
+    return wide_mt_rows(spec, xt, z_dn, hyp, zip_pairs, entry="fgp_mt_rows")
+
+
+def mt_pair_rows(spec, xt, z_dn, hyp, zip_pairs=False):
+    """The kernel rows of a fused task-pair spec at any d <= 64: mt_rows or wide_mt_rows by spec.d."""
+    return (wide_mt_rows if _wide(spec.d) else mt_rows)(spec, xt, z_dn, hyp, zip_pairs)
 
 
 MT_WIDE_POST_MEAN_BYTES = 1 << 22   # default rule of the matrix-free multitask mean: kernel rows beyond this many bytes
 
 
 def mt_wide_post_mean_route(rows_bytes):
-    """The route of a multitask post_mean at d > 8 whose task pairs all have a fused spec: the matrix-free sum
-    (fgp_mt_wide_post_mean) or the kernel rows and an einsum.  FGP_WIDE_MT_POST_MEAN=1: the sum at any size; =0: the rows
-    everywhere (A/B runs); default: the sum when the rows array, rows_bytes = 8 B T' N sum n, exceeds
-    MT_WIDE_POST_MEAN_BYTES.  The rows route allocates that array several times over, so the rule bounds post_mean's
-    memory well inside MT_POST_VAR_QF_BYTES; it stands at 2^22 and not at 2^28 because the sum was measured faster at
-    every size from 1.2 MB to 4.8 GB of rows (no crossover found), and not lower because the
-    routing test of a 60 x 8192 prediction (3.9 MB) counts its fgp_wide_mt_rows calls."""
+    """The route of a multitask post_mean whose task pairs all have a fused spec, at d > 8 and (the name is kept) at
+    d <= 8 alike: the matrix-free sum (fgp_mt_wide_post_mean / fgp_mt_post_mean) or the kernel rows and an einsum.
+    FGP_WIDE_MT_POST_MEAN=1: the sum at any size; =0: the rows everywhere (A/B runs); default: the sum when the rows
+    array, rows_bytes = 8 B T' N sum n, exceeds MT_WIDE_POST_MEAN_BYTES.  The rows route allocates that array several
+    times over, so the rule bounds post_mean's memory well inside MT_POST_VAR_QF_BYTES.  It stands at 2^22 and not at
+    2^28 because the sum was measured faster at every size: at d > 8 from 1.2 MB to 4.8 GB of rows (DESIGN.md section
+    3.5), at d <= 8 from 18 MB to 1.2 GB (0.64 against 3.5 ms at 18 MB, section 4; smaller rows were not measured
+    there, and no crossover was found in either range).  It is not lower because the routing test of a 60 x 8192
+    prediction at d > 8 (3.9 MB) counts its fgp_wide_mt_rows calls."""
     env = os.environ.get("FGP_WIDE_MT_POST_MEAN", "")[:1]
     if env in ("0", "1"):
         return env == "1"
     return rows_bytes > MT_WIDE_POST_MEAN_BYTES
 
 
-def mt_wide_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0):
+def mt_wide_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0, entry="fgp_mt_wide_post_mean"):
     """out[b, t] = beta out[b, t] + w[b] sum_i K_ab^{(g(b))}(xt[t], z[:, i]) coeffs[b, i] in place
     (fgp_mt_wide_post_mean), no kernel row stored: xt [N, d] float64 test points, z_dn [d, n] dimension-major (float64
     lattice / int64 net), hyp [Gk, 1 + d] with Gk in {1, B} (g(b) = b or 0), coeffs [B, n] and out [B, N] float64 with
     unit inner stride (views of wider rows are taken as they are), w [B] or None (1), beta 0 or 1.  chunk: the entry
     point's chunk of training points (0: its default)."""
-    require_device(xt, "mt_wide_post_mean")
+    require_device(xt, entry[4:])
     xt = xt.to(torch.float64).contiguous()
     Nt, d = xt.shape
     n = z_dn.shape[1]
@@ -921,12 +945,23 @@ def mt_wide_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0):
     cs = coeffs.stride(0) if B > 1 else n
     os_ = out.stride(0) if B > 1 else Nt
     wlen = ctypes.c_int64(0)
-    N.call("fgp_mt_wide_post_mean_work", Nt, n, B, int(chunk), ctypes.byref(wlen))
+    N.call(entry + "_work", Nt, n, B, int(chunk), ctypes.byref(wlen))
     work = torch.empty((wlen.value,), dtype=torch.float64, device=xt.device)
-    N.call("fgp_mt_wide_post_mean", spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, spec.P, spec.order, spec.coef, spec.add,
+    N.call(entry, spec.family, N.ptr(xt), Nt, N.ptr(z_dn), n, d, spec.P, spec.order, spec.coef, spec.add,
            spec.ind, spec.cc, spec.tbits, N.ptr(hyp), Gk, N.ptr(coeffs), cs, B, N.ptr(w), int(beta), N.ptr(out), os_,
            N.ptr(work), int(chunk), _stream(xt))
     return out
+
+
+def mt_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0):
+    """mt_wide_post_mean for d <= 8 (fgp_mt_post_mean): the same arguments and result."""
+    return mt_wide_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk, entry="fgp_mt_post_mean")
+
+
+def mt_pair_post_mean(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk=0):
+    """One task pair's share of the matrix-free posterior mean at any d <= 64: mt_post_mean or mt_wide_post_mean by
+    spec.d."""
+    return (mt_wide_post_mean if _wide(spec.d) else mt_post_mean)(spec, xt, z_dn, hyp, coeffs, w, out, beta, chunk)
 
 
 def mt_factor(lay, lams):

@@ -685,6 +685,31 @@ extern int fgp_mt_wide_post_mean(int family, const double* xt, int64_t N, const 
                                  double* work, int64_t chunk, void* stream);
 
 
+/* Addition to ABI 20 -- the task-pair kernel and the matrix-free posterior mean above for 1 <= d <= FGP_MAX_D (the
+ * predictions of multitask / derivative-informed GPs at d <= 8, beside fgp_mt_parts and the caller's torch formulation
+ * over its [N][M][P][d] parts array).  Arguments, layouts, limits and the summation contract are those of
+ * fgp_wide_mt_rows / fgp_mt_wide_post_mean_work / fgp_mt_wide_post_mean: z dimension-major [d][n], hyp [Gk][1 + d], host
+ * spec tables [P][d] (add may be NULL for lattices) and cc [P], 1 <= P <= FGP_WIDE_MT_MAX_P, N <= 65535 per rows call
+ * (zip: any N == n), the mean splits its test points inside, N == 0: FGP_OK without a launch.  A part has the
+ * arithmetic of fgp_mt_parts (it carries the bits that entry point writes); the product runs in ascending j, the sum
+ * in ascending p, then the scale; the value under the mean's sum carries the bits fgp_mt_rows writes, and a test point
+ * has the same bits predicted alone or among others.  The tables travel by value in the kernels' argument block:
+ * nothing is uploaded or cached, and no call blocks.
+ * Validation before any HIP call (also without a device), naming the argument: d outside 1 .. FGP_MAX_D, P < 1, a
+ * negative size, a null pointer, tbits outside 1 .. 63 for nets, an ind entry other than 0 / 1, Gk outside {1, B}, beta
+ * outside {0, 1}, a bad chunk, a row stride below its row: FGP_ERR_INVALID; P > FGP_WIDE_MT_MAX_P or an order outside
+ * its range (lattice 1 .. 8, net 1 .. 4): FGP_ERR_UNSUPPORTED. */
+extern int fgp_mt_rows(int family, const double* xt, int64_t N, const void* z, int64_t n, int zip, int d, int P,
+                       const int* order, const double* coef, const double* add, const int* ind, const double* cc,
+                       int tbits, const double* hyp, int Gk, double* rows, void* stream);
+extern int fgp_mt_post_mean_work(int64_t N, int64_t n, int B, int64_t chunk, int64_t* len);
+extern int fgp_mt_post_mean(int family, const double* xt, int64_t N, const void* z, int64_t n, int d, int P,
+                            const int* order, const double* coef, const double* add, const int* ind, const double* cc,
+                            int tbits, const double* hyp, int Gk, const double* coeffs, int64_t coeff_stride, int B,
+                            const double* w, int beta, double* out, int64_t out_stride, double* work, int64_t chunk,
+                            void* stream);
+
+
 /* Natural-order digital net points (FastGPDigitalNetB2's sequences, fast_gp_digital_net_b2.py:266-273):
  * xb[i - n_min][j] = XOR_{k: bit k of i} C[j][k] XOR shift[j] (t-bit ints), x = xb 2^-t; C [d][mcols] and
  * shift [d] are DEVICE uint64 arrays; xb [n][d] int64 and / or x [n][d] float64 (either may be NULL). */
