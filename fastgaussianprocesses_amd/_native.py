@@ -143,8 +143,15 @@ class WideMtFitDesc(ctypes.Structure):
     ]
 
 
+class WideMtFitBatchDesc(ctypes.Structure):
+    """Mirror of fgp_wide_mt_fit_batch_desc (include/fgp_hip.h, an addition to ABI 20): the one-problem descriptor
+    followed by the parameter-batch fields."""
+    _fields_ = [("one", WideMtFitDesc), ("G", _c_int), ("rows", _c_vp), ("nrows", _c_int * 5)]
+
+
 _P_NLL = ctypes.POINTER(NllDesc)
 _P_WIDEMTFIT = ctypes.POINTER(WideMtFitDesc)
+_P_WIDEMTFITB = ctypes.POINTER(WideMtFitBatchDesc)
 _P_WIDEFIT = ctypes.POINTER(WideFitDesc)
 _P_MTFIT = ctypes.POINTER(MtFitDesc)
 _P_MT = ctypes.POINTER(MtLayout)
@@ -270,6 +277,13 @@ _SIGNATURES = {
     "fgp_wide_mt_fit_stage": [_P_WIDEMTFIT, _c_int, _c_int, _c_int, _c_vp],
     # addition to ABI 20: test hook -- where the GCV / CV partials of fgp_wide_mt_fit_run lie in `work`
     "fgp_wide_mt_fit_loss_layout": [_P_WIDEMTFIT, _c_pl],
+    # addition to ABI 20: the wide multitask fit loop over a parameter batch (the one-problem entry points' counterparts)
+    "fgp_wide_mt_fit_batch_work": [_P_WIDEMTFITB, _c_pl],
+    "fgp_wide_mt_fit_batch_run": [_P_WIDEMTFITB, _c_int, _c_int, _c_int, _c_vp],
+    "fgp_wide_mt_fit_batch_work_layout": [_P_WIDEMTFITB, _c_pl],
+    "fgp_wide_mt_fit_batch_stage": [_P_WIDEMTFITB, _c_int, _c_int, _c_int, _c_vp],
+    # test hook -- where the per-problem totals lie in `work`
+    "fgp_wide_mt_fit_batch_layout": [_P_WIDEMTFITB, _c_pl],
 }
 
 

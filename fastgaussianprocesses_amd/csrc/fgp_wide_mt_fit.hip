@@ -24,6 +24,14 @@
 // loop's .to(complex128) passes the real part of the gradient back).  fgp_wide_mt_k1 / _k1_bwd take their spec by
 // value (no device table, no copy), so validating every pair's spec before the first launch is all the "first use"
 // there is; the transforms' twiddle tables are made on their first call as everywhere else.
+//
+// PARAMETER batches (fgp_wide_mt_fit_batch_desc: G > 1 problems, each with its own rows of the five parameter blocks; the work
+// layout and the bit contract are stated in include/fgp_hip.h): the same stages over G problems, the launch count
+// independent of G.  k1 / transforms / k1_bwd take a pair's G rows in one call (A and B are pair-major [p][G][n_k]), the
+// block calls take G problems (lams .. glp problem-major [G][L]), k_wide_mt_lams / k_wide_mt_contract get the problem as
+// blockIdx.z, and the one-workgroup step is split in two: k_wide_mt_fit_sums (a workgroup per problem: the evaluation
+// half) and k_wide_mt_fit_bstep (element sums over the problems, loss row, histories, Rprop, natural rows) -- one call
+// more.  With G <= 1 every index below reduces to the one-problem one and k_wide_mt_fit_step runs as before.
 #include <cmath>
 #include <cstdint>
 
@@ -37,12 +45,16 @@ namespace fgp {
 constexpr int kWmfT = FGP_MT_MAX_TASKS;
 constexpr int kWmfPairs = FGP_WIDE_MT_FIT_PAIRS;
 constexpr int kWmfMaxParams = 2 + FGP_WIDE_MAX_D + kWmfT * kWmfT + kWmfT;
+constexpr int kWmfMaxG = 4096;               // problems of a parameter batch, raw elements of all their rows
+constexpr int kWmfMaxBatchParams = 8192;
 
 // what the new kernels need of the problem, by value
 struct WmfLay {
   int T, np;                       // sorted active tasks, pairs
   int T_all, rank, vtask_exp;
-  int f_off, v_off, noise_off;     // raw offsets of the task factor, the task noise and the noise
+  int f_off, v_off, noise_off;     // raw offsets of the task factor, the task noise and the noise (G > 1: of row 0)
+  int G;                           // problems (>= 1)
+  int64_t L;                       // packed length of one problem
   int64_t n[kWmfT];                // descending
   int64_t offk[kWmfT];             // packed offset of pair (k, k); pair (k, l) at offk[k] + (l - k) n[k]
   int task[kWmfT];                 // task index a_k of sorted task k
@@ -61,11 +73,35 @@ __device__ __forceinline__ void wmf_pair(const WmfLay& m, int p, int& k, int& l)
 }
 
 // K_task[a, b] = sum_r F[a, r] F[b, r] + [a == b] v_a from the raw rows (mtg_kt, fgp_multitask.hip; util.py:157-162)
-__device__ __forceinline__ double wmf_kt(const WmfLay& m, const double* __restrict__ raw, int a, int b) {
+// (f_off, v_off: the raw offsets of the problem's task-factor and task-noise rows)
+__device__ __forceinline__ double wmf_kt(const WmfLay& m, const double* __restrict__ raw, int f_off, int v_off, int a,
+                                         int b) {
   double s = 0.0;
-  for (int r = 0; r < m.rank; ++r) s += raw[m.f_off + a * m.rank + r] * raw[m.f_off + b * m.rank + r];
-  if (a == b) s += m.vtask_exp ? exp(raw[m.v_off + a]) : raw[m.v_off + a];
+  for (int r = 0; r < m.rank; ++r) s += raw[f_off + a * m.rank + r] * raw[f_off + b * m.rank + r];
+  if (a == b) s += m.vtask_exp ? exp(raw[v_off + a]) : raw[v_off + a];
   return s;
+}
+
+// the raw offsets of problem g's noise, task-factor and task-noise rows (rows [5][G]; NULL: row 0 of every block)
+struct WmfOff {
+  int noise, f, v;
+};
+__device__ __forceinline__ WmfOff wmf_off(const WmfLay& m, const int* __restrict__ rows, int g) {
+  WmfOff o;
+  o.noise = m.noise_off, o.f = m.f_off, o.v = m.v_off;
+  if (rows) {
+    o.noise += rows[2 * m.G + g];
+    o.f += rows[3 * m.G + g] * m.T_all * m.rank;
+    o.v += rows[4 * m.G + g] * m.T_all;
+  }
+  return o;
+}
+// element i of sorted pair (k, l) of problem g: in the pair-major transform arrays A / B, in the problem-major packed ones
+__device__ __forceinline__ int64_t wmf_epair(const WmfLay& m, int k, int l, int g, int64_t i) {
+  return (int64_t)m.G * m.offk[k] + ((int64_t)(l - k) * m.G + g) * m.n[k] + i;
+}
+__device__ __forceinline__ int64_t wmf_eprob(const WmfLay& m, int k, int l, int g, int64_t i) {
+  return (int64_t)g * m.L + m.offk[k] + (int64_t)(l - k) * m.n[k] + i;
 }
 
 template <int FAM>
@@ -80,24 +116,26 @@ __device__ __forceinline__ double2 wmf_lam(const void* __restrict__ lam, int64_t
 
 // ------------------------------------------------------------------------------------------------
 // lams[k, l][i] = K_task[a_k, a_l] (sqrt(n_l) lam^_kl[i] + noise [k == l])  (util.py:284-298), thread = entry i of pair
-// p = blockIdx.y.  lam: complex128 (FAM 0) / float64 (FAM 1), packed as the lams.
+// p = blockIdx.y of problem g = blockIdx.z.  lam: complex128 (FAM 0) / float64 (FAM 1), pair-major [p][G][n_k]; lams
+// problem-major [G][L] (one problem: both are the packed layout).
 template <int FAM>
 __global__ __launch_bounds__(kWG) void k_wide_mt_lams(WmfLay m, const double* __restrict__ raw,
-                                                      const void* __restrict__ lam, double2* __restrict__ lams) {
-  const int p = blockIdx.y;
+                                                      const int* __restrict__ rows, const void* __restrict__ lam,
+                                                      double2* __restrict__ lams) {
+  const int p = blockIdx.y, g = blockIdx.z;
   int k, l;
   wmf_pair(m, p, k, l);
   const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
   if (i >= m.n[k]) return;
-  const int64_t e = m.offk[k] + (int64_t)(l - k) * m.n[k] + i;
+  const WmfOff o = wmf_off(m, rows, g);
   const bool cj = (m.conj[p >> 6] >> (p & 63)) & 1ull;
-  const double2 v = wmf_lam<FAM>(lam, e, cj);
+  const double2 v = wmf_lam<FAM>(lam, wmf_epair(m, k, l, g, i), cj);
   const double rn = sqrt((double)m.n[l]);
   double bx = rn * v.x;
   const double by = rn * v.y;
-  if (k == l) bx += exp(raw[m.noise_off]);
-  const double kt = wmf_kt(m, raw, m.task[k], m.task[l]);
-  lams[e] = make_double2(bx * kt, by * kt);
+  if (k == l) bx += exp(raw[o.noise]);
+  const double kt = wmf_kt(m, raw, o.f, o.v, m.task[k], m.task[l]);
+  lams[wmf_eprob(m, k, l, g, i)] = make_double2(bx * kt, by * kt);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -107,14 +145,19 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_lams(WmfLay m, const double* __
 //   part[p][1][blk]    = sum_i Re(conj(g[i]) (sqrt(n_l) lam^[i] + noise [k == l]))   (dL/dK_task[a_k, a_l])
 // blockIdx.y == np: part[np][0][blk] = this workgroup's share of sum_b Re(conj(y_b) z_b), part[np][1][blk] of the
 // classes' logdet.  A workgroup past its pair's n_k writes nothing, and the step reads none of its partials.
+// Problem g = blockIdx.z: its yz_len entries of y and z, its nmin classes of logdet, its [np + 1][2][nbx] of part.
 template <int FAM>
 __global__ __launch_bounds__(kWG) void k_wide_mt_contract(WmfLay m, const double* __restrict__ raw,
+                                                          const int* __restrict__ rows,
                                                           const double2* __restrict__ glp, void* __restrict__ lam,
                                                           const double2* __restrict__ y, const double2* __restrict__ z,
                                                           int64_t yz_len, const double* __restrict__ logdet, int nbx,
                                                           double* __restrict__ part) {
   __shared__ double red[kWG / 64];
-  const int p = blockIdx.y;
+  const int p = blockIdx.y, g = blockIdx.z;
+  y += (int64_t)g * yz_len, z += (int64_t)g * yz_len;
+  logdet += (int64_t)g * m.n[m.T - 1];
+  part += (int64_t)g * (m.np + 1) * 2 * nbx;
   double s0 = 0.0, s1 = 0.0;
   if (p == m.np) {
     const int64_t t0 = (int64_t)blockIdx.x * kWG + threadIdx.x, nt = (int64_t)nbx * kWG;
@@ -129,19 +172,20 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_contract(WmfLay m, const double
     if ((int64_t)blockIdx.x * kWG >= m.n[k]) return;
     const int64_t i = (int64_t)blockIdx.x * kWG + threadIdx.x;
     if (i < m.n[k]) {
-      const int64_t e = m.offk[k] + (int64_t)(l - k) * m.n[k] + i;
+      const WmfOff o = wmf_off(m, rows, g);
+      const int64_t e = wmf_epair(m, k, l, g, i);
       const bool cj = (m.conj[p >> 6] >> (p & 63)) & 1ull;
       const double2 v = wmf_lam<FAM>(lam, e, cj);
-      const double2 g = glp[e];
+      const double2 gv = glp[wmf_eprob(m, k, l, g, i)];
       const double rn = sqrt((double)m.n[l]);
       double bx = rn * v.x;
       const double by = rn * v.y;
-      if (k == l) bx += exp(raw[m.noise_off]);
-      const double f = wmf_kt(m, raw, m.task[k], m.task[l]) * rn;
-      s0 = g.x;
-      s1 = __builtin_fma(g.x, bx, g.y * by);
-      if constexpr (FAM == 0) static_cast<double2*>(lam)[e] = make_double2(f * g.x, cj ? -(f * g.y) : f * g.y);
-      else static_cast<double*>(lam)[e] = f * g.x;
+      if (k == l) bx += exp(raw[o.noise]);
+      const double f = wmf_kt(m, raw, o.f, o.v, m.task[k], m.task[l]) * rn;
+      s0 = gv.x;
+      s1 = __builtin_fma(gv.x, bx, gv.y * by);
+      if constexpr (FAM == 0) static_cast<double2*>(lam)[e] = make_double2(f * gv.x, cj ? -(f * gv.y) : f * gv.y);
+      else static_cast<double*>(lam)[e] = f * gv.x;
     }
   }
   s0 = block_sum(s0, red);
@@ -321,6 +365,82 @@ struct WmfStep {
   const double* pl;          // GCV / CV: k_wide_mt_loss_sums' partials [NT][2][nbx]
 };
 
+// The second level of one problem's sums (the evaluation half of the step, shared by k_wide_mt_fit_step and
+// k_wide_mt_fit_sums): tot[2 p + q] of part [np + 1][2][nbx] -- a lane over every kWG-th partial ascending, then
+// block_sum; only the first ceil(n_k / kWG) partials of a pair, and of q = 0 the diagonal pairs only -- and dsum[0 .. d]
+// = the sum over the pairs, ascending, of dscale / dls[j] (pair p's at ds + p ds_pair and dlp + j + p ds_pair).  Ends with a
+// barrier.
+__device__ __forceinline__ void wmf_second_level(const WmfLay& m, int d, int nbx, const double* __restrict__ part,
+                                                 const double* __restrict__ ds, const double* __restrict__ dlp,
+                                                 int64_t ds_pair, double* red, double* tot, double* dsum) {
+  const int tid = threadIdx.x, np = m.np;
+  for (int p = 0; p <= np; ++p) {
+    int k = 0, l = 0;
+    int64_t cnt = nbx;
+    if (p < np) {
+      wmf_pair(m, p, k, l);
+      cnt = (m.n[k] + kWG - 1) / kWG;
+    }
+    for (int q = 0; q < 2; ++q) {
+      if (p < np && q == 0 && k != l) continue;        // Re g sums: the diagonal pairs only
+      const double* pq = part + ((int64_t)p * 2 + q) * nbx;
+      double a = 0.0;
+      for (int64_t c = tid; c < cnt; c += kWG) a += pq[c];
+      a = block_sum(a, red);
+      if (tid == 0) tot[2 * p + q] = a;
+    }
+  }
+  if (tid <= d) {
+    double a = 0.0;
+    for (int p = 0; p < np; ++p) a += (tid == 0 ? ds : dlp + (tid - 1))[(int64_t)p * ds_pair];
+    dsum[tid] = a;
+  }
+  __syncthreads();
+}
+
+// One problem's raw gradient of its own parameter x, x in one problem's order [scale, dl lengthscales, noise, task factor
+// T_all x rank, task noise T_all]; o: the raw offsets of the problem's noise, factor and task-noise rows; nat_s, nat_l: its
+// natural scale and lengthscales.
+__device__ __forceinline__ double wmf_raw_grad(const WmfLay& m, int d, int dl, int x, const double* __restrict__ raw,
+                                               const WmfOff& o, double nat_s, const double* __restrict__ nat_l,
+                                               const double* tot, const double* dsum) {
+  const int noise1 = 1 + dl, f1 = noise1 + 1, v1 = f1 + m.T_all * m.rank;
+  double gs = 0.0;
+  if (x == 0) {
+    gs = nat_s * dsum[0];                                              // exp transforms: d nat / d raw = nat
+  } else if (x < noise1) {
+    const int j = x - 1;
+    if (dl == d) {
+      gs = nat_l[j] * dsum[1 + j];
+    } else {                                                            // one lengthscale: the sum over j, ascending
+      double a = 0.0;
+      for (int jj = 0; jj < d; ++jj) a += dsum[1 + jj];
+      gs = nat_l[0] * a;
+    }
+  } else if (x == noise1) {
+    double a = 0.0;
+    for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k) a += wmf_kt(m, raw, o.f, o.v, m.task[k], m.task[k]) * tot[2 * p];
+    gs = exp(raw[o.noise]) * a;
+  } else if (x < v1) {
+    // K_task[a, b] = sum_r F[a, r] F[b, r] + [a == b] v_a:  dF[c, r] += g_ab (F[b, r] [a == c] + F[a, r] [b == c])
+    const int u = x - f1, c = u / m.rank, r = u - c * m.rank;
+    for (int k = 0, p = 0; k < m.T; ++k) {
+      const int a = m.task[k];
+      for (int l = k; l < m.T; ++l, ++p) {
+        const int b = m.task[l];
+        const double gv = tot[2 * p + 1];
+        if (a == c) gs += gv * raw[o.f + b * m.rank + r];
+        if (b == c) gs += gv * raw[o.f + a * m.rank + r];
+      }
+    }
+  } else {
+    const int c = x - v1;
+    for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k)
+      if (m.task[k] == c) gs += m.vtask_exp ? tot[2 * p + 1] * exp(raw[o.v + c]) : tot[2 * p + 1];
+  }
+  return gs;
+}
+
 __global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, int mode, int init) {
   __shared__ double red[kWG / 64];
   __shared__ double tot[2 * (kWmfPairs + 1)];     // [p][0 / 1]: the second-level sums of part
@@ -331,65 +451,10 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, i
   const WmfLay& m = s.lay;
   const int d = s.d, dl = s.dl, np = m.np, n_params = f.n_params;
   if (mode != 0) {
-    for (int p = 0; p <= np; ++p) {
-      int k = 0, l = 0;
-      int64_t cnt = s.nbx;
-      if (p < np) {
-        wmf_pair(m, p, k, l);
-        cnt = (m.n[k] + kWG - 1) / kWG;
-      }
-      for (int q = 0; q < 2; ++q) {
-        if (p < np && q == 0 && k != l) continue;        // Re g sums: the diagonal pairs only
-        const double* pq = s.part + ((int64_t)p * 2 + q) * s.nbx;
-        double a = 0.0;
-        for (int64_t c = tid; c < cnt; c += kWG) a += pq[c];
-        a = block_sum(a, red);
-        if (tid == 0) tot[2 * p + q] = a;
-      }
-    }
-    if (tid <= d) {
-      double a = 0.0;
-      for (int p = 0; p < np; ++p) a += s.dsl[(int64_t)p * (1 + d) + tid];
-      dsum[tid] = a;
-    }
-    __syncthreads();
+    wmf_second_level(m, d, s.nbx, s.part, s.dsl, s.dsl + 1, 1 + d, red, tot, dsum);
     // the raw gradient of every parameter, before any parameter moves (the task-factor rows read one another)
-    for (int x = tid; x < n_params; x += kWG) {
-      double gs = 0.0;
-      if (x == 0) {
-        gs = s.nat[0] * dsum[0];                                         // exp transforms: d nat / d raw = nat
-      } else if (x < m.noise_off) {
-        const int j = x - 1;
-        if (dl == d) {
-          gs = s.nat[1 + j] * dsum[1 + j];
-        } else {                                                          // one lengthscale: the sum over j, ascending
-          double a = 0.0;
-          for (int jj = 0; jj < d; ++jj) a += dsum[1 + jj];
-          gs = s.nat[1] * a;
-        }
-      } else if (x == m.noise_off) {
-        double a = 0.0;
-        for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k) a += wmf_kt(m, f.raw, m.task[k], m.task[k]) * tot[2 * p];
-        gs = exp(f.raw[x]) * a;
-      } else if (x < m.v_off) {
-        // K_task[a, b] = sum_r F[a, r] F[b, r] + [a == b] v_a:  dF[c, r] += g_ab (F[b, r] [a == c] + F[a, r] [b == c])
-        const int u = x - m.f_off, c = u / m.rank, r = u - c * m.rank;
-        for (int k = 0, p = 0; k < m.T; ++k) {
-          const int a = m.task[k];
-          for (int l = k; l < m.T; ++l, ++p) {
-            const int b = m.task[l];
-            const double gv = tot[2 * p + 1];
-            if (a == c) gs += gv * f.raw[m.f_off + b * m.rank + r];
-            if (b == c) gs += gv * f.raw[m.f_off + a * m.rank + r];
-          }
-        }
-      } else {
-        const int c = x - m.v_off;
-        for (int k = 0, p = 0; k < m.T; p += m.T - k, ++k)
-          if (m.task[k] == c) gs += m.vtask_exp ? tot[2 * p + 1] * exp(f.raw[x]) : tot[2 * p + 1];
-      }
-      grad[x] = gs;
-    }
+    const WmfOff o = wmf_off(m, nullptr, 0);
+    for (int x = tid; x < n_params; x += kWG) grad[x] = wmf_raw_grad(m, d, dl, x, f.raw, o, s.nat[0], s.nat + 1, tot, dsum);
     if (s.loss != FGP_LOSS_MLL) {
       // GCV / CV: the second level of the loss sums in k_wide_mt_loss_grad's order; the row (loss, N, D) or
       // (loss, NaN, NaN); tot[2 np], tot[2 np + 1], mll_const and w are unread
@@ -444,6 +509,105 @@ __global__ __launch_bounds__(kWG) void k_wide_mt_fit_step(WmfStep s, int iter, i
   for (int j = tid; j < d; j += kWG) s.nat[1 + j] = exp(f.raw[1 + (dl == d ? j : 0)]);
 }
 
+// ------------------------------------------------------------------------------------------------ G > 1 problems
+// The evaluation half of the step for problem g = blockIdx.x: sums[g] = (norm_g, logdet_g, the problem's raw-space
+// contribution to each of its own P1 = 2 + dl + T_all rank + T_all parameters), by wmf_second_level and wmf_raw_grad --
+// the sums, the order and the expressions of k_wide_mt_fit_step on this problem alone.  LDS: 8 (4 + 2 (np + 1) + 1 + 64)
+// <= 2.7 KB, static.
+struct WmfSums {
+  WmfLay lay;
+  int d, dl, nbx;
+  const double* raw;
+  const int* rows;           // [5][G]
+  const double* part;        // [G][np + 1][2][nbx]
+  const double* dsl;         // per pair dscale [G], then dls [G][d]
+  const double* nat;         // scale [G], then lengthscales [G][d]
+  double* sums;              // [G][2 + P1]
+};
+
+__global__ __launch_bounds__(kWG) void k_wide_mt_fit_sums(WmfSums s) {
+  __shared__ double red[kWG / 64];
+  __shared__ double tot[2 * (kWmfPairs + 1)];
+  __shared__ double dsum[1 + FGP_WIDE_MAX_D];
+  const WmfLay& m = s.lay;
+  const int g = blockIdx.x, G = m.G, d = s.d, dl = s.dl, np = m.np;
+  const int P1 = 2 + dl + m.T_all * m.rank + m.T_all;
+  wmf_second_level(m, d, s.nbx, s.part + (int64_t)g * (np + 1) * 2 * s.nbx, s.dsl + g, s.dsl + G + (int64_t)g * d,
+                   (int64_t)G * (1 + d), red, tot, dsum);
+  const WmfOff o = wmf_off(m, s.rows, g);
+  double* out = s.sums + (int64_t)g * (2 + P1);
+  for (int x = threadIdx.x; x < P1; x += kWG)
+    out[2 + x] = wmf_raw_grad(m, d, dl, x, s.raw, o, s.nat[g], s.nat + G + (int64_t)g * d, tot, dsum);
+  if (threadIdx.x == 0) out[0] = tot[2 * np], out[1] = tot[2 * np + 1];
+}
+
+// The step over G problems, one workgroup of kWmfStepWG threads, a thread per raw element (strided).  Modes as
+// k_wide_mt_fit_step.  Element x of row r of block q gets the sum of sums[g][its column] over the problems g with
+// rows[q][g] == r, g ascending from 0.0 (k_mtg_step's order, fgp_multitask.hip); thread 0 adds the loss terms, g
+// ascending.  The gradients come from sums alone, so an element is read, stepped and written by its own thread and no
+// gradient is staged: no LDS.  The natural rows of the new parameters are gathered after a barrier.
+constexpr int kWmfStepWG = 1024;
+struct WmfBStep {
+  Fit f;
+  int G, d, dl, T_all, rank;
+  int nrows[5];
+  int rg_factor, rg_vtask;
+  double w, lr;
+  const int* rows;           // [5][G]
+  const double* sums;        // [G][2 + P1]
+  double* nat;               // scale [G], then lengthscales [G][d]
+  double* gn;                // [G] = 1/2, then gl [G] = 1/2 w
+  int* info;
+};
+
+__global__ __launch_bounds__(kWmfStepWG) void k_wide_mt_fit_bstep(WmfBStep s, int iter, int mode, int init) {
+  const int tid = threadIdx.x;
+  const Fit& f = s.f;
+  const int G = s.G, d = s.d, dl = s.dl, n_params = f.n_params;
+  if (mode != 0) {
+    const int wid[5] = {1, dl, 1, s.T_all * s.rank, s.T_all};
+    const int col0[5] = {0, 1, 1 + dl, 2 + dl, 2 + dl + s.T_all * s.rank};     // a block's first column of P1
+    const int rgs[5] = {f.scale_rg, f.ls_rg, f.noise_rg, s.rg_factor, s.rg_vtask};
+    const int S = 2 + col0[4] + s.T_all;
+    for (int x = tid; x < n_params; x += kWmfStepWG) {
+      int q = 0, base = 0;
+      while (q < 4 && x >= base + s.nrows[q] * wid[q]) base += s.nrows[q] * wid[q], ++q;
+      const int r = (x - base) / wid[q], c = 2 + col0[q] + (x - base) - r * wid[q];
+      const int* rq = s.rows ? s.rows + (int64_t)q * G : nullptr;
+      double gp = 0.0;
+      for (int g = 0; g < G; ++g)
+        if ((rq ? rq[g] : 0) == r) gp += s.sums[(int64_t)g * S + c];
+      f.raw_hist[(int64_t)iter * n_params + x] = f.raw[x];
+      f.grad_out[x] = gp;
+      if (mode == 2 && rgs[q]) rprop_update(f, x, gp);
+    }
+    if (tid == 0) {
+      double t1 = 0.0, ld = 0.0;
+      for (int g = 0; g < G; ++g) t1 += s.sums[(int64_t)g * S], ld += s.sums[(int64_t)g * S + 1];
+      const double t2 = s.w * ld;
+      double* lh = f.loss_hist + (int64_t)iter * 3;
+      lh[0] = 0.5 * (t1 + t2) + f.mll_const;
+      lh[1] = t1;
+      lh[2] = t2;
+    }
+    if (mode != 2) return;
+    __syncthreads();
+  } else {
+    if (init)
+      for (int x = tid; x < n_params; x += kWmfStepWG) {
+        f.prev[x] = 0.0;
+        f.step[x] = s.lr;
+      }
+    for (int b = tid; b < 2 * G; b += kWmfStepWG) s.gn[b] = b < G ? 0.5 : 0.5 * s.w;
+    if (tid == 0) s.info[0] = 0;
+  }
+  for (int g = tid; g < G; g += kWmfStepWG) s.nat[g] = exp(f.raw[s.rows ? s.rows[g] : 0]);
+  for (int e = tid; e < G * d; e += kWmfStepWG) {
+    const int g = e / d, j = e - g * d;
+    s.nat[G + e] = exp(f.raw[s.nrows[0] + (s.rows ? s.rows[G + g] : 0) * dl + (dl == d ? j : 0)]);
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ host side
 struct WmfPlan {
   WmfLay lay;
@@ -455,12 +619,21 @@ struct WmfPlan {
   // byte offsets into work
   size_t o_nat, o_gn, o_info, o_dsl, o_a, o_b, o_w, o_lams, o_fac, o_zinv, o_glp, o_z, o_ld, o_part, o_pb, bytes;
   size_t o_pl, pl_bytes;                           // GCV / CV: k_wide_mt_loss_sums' partials, after pb (MLL: empty)
+  int G, P1;                                       // problems (>= 1), one problem's parameters
+  int nrows[5];                                    // rows per parameter block (>= 1)
+  const int* rows;                                 // G > 1: device [5][G] (may be NULL: row 0), else NULL
+  size_t o_sums, sums_bytes;                       // G > 1: the per-problem totals [G][2 + P1], after pl (else empty)
 };
 
 static size_t wmf_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
+// bt: the batch descriptor whose `one` is a, or NULL (one problem)
+static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p,
+                    const fgp_wide_mt_fit_batch_desc* bt = nullptr) {
   if (!a) return set_error(kErrInvalid, "%s: null pointer: desc", fn);
+  static const int kNoRows[5] = {0, 0, 0, 0, 0};
+  const int G_in = bt ? bt->G : 0;
+  const int* nrows_in = bt ? bt->nrows : kNoRows;
   if (a->d <= FGP_MAX_D || a->d > FGP_WIDE_MAX_D)
     return set_error(kErrInvalid, "%s: d=%d outside %d..%d", fn, a->d, FGP_MAX_D + 1, FGP_WIDE_MAX_D);
   if (a->family != FGP_FAMILY_LATTICE && a->family != FGP_FAMILY_NET)
@@ -517,36 +690,68 @@ static int wmf_plan(const char* fn, const fgp_wide_mt_fit_desc* a, WmfPlan& p) {
                        FGP_WIDE_MT_MAX_P);
     if (a->pair[q].conj) m.conj[q >> 6] |= 1ull << (q & 63);
   }
+  // parameter batches: G problems (0 = 1), nrows[q] rows of block q (0 = 1)
+  if (G_in < 0) return set_error(kErrInvalid, "%s: G=%d negative", fn, G_in);
+  p.G = G_in > 1 ? G_in : 1;
+  p.rows = p.G > 1 ? bt->rows : nullptr;
+  const int wid[5] = {1, a->dl, 1, a->T_all * a->rank, a->T_all};
+  p.P1 = 0;
+  int64_t npar = 0;
+  for (int q = 0; q < 5; ++q) {
+    if (nrows_in[q] < 0) return set_error(kErrInvalid, "%s: nrows[%d]=%d negative", fn, q, nrows_in[q]);
+    p.nrows[q] = nrows_in[q] > 1 ? nrows_in[q] : 1;
+    if (p.G == 1 && p.nrows[q] > 1)
+      return set_error(kErrInvalid, "%s: nrows[%d]=%d rows for G=%d (one problem has one row per block)", fn, q,
+                       nrows_in[q], G_in);
+    p.P1 += wid[q];
+    npar += (int64_t)p.nrows[q] * wid[q];
+  }
+  if (p.G > 1) {
+    if (a->B != 1)
+      return set_error(kErrUnsupported, "%s: B=%d with G=%d (a parameter batch has one data vector per problem)", fn, a->B,
+                       G_in);
+    if (loss != FGP_LOSS_MLL)
+      return set_error(kErrUnsupported, "%s: loss_metric=%d with G=%d (a parameter batch fits the MLL)", fn, loss, G_in);
+    if (p.G > kWmfMaxG) return set_error(kErrUnsupported, "%s: G=%d problems above %d", fn, G_in, kWmfMaxG);
+    if (npar > kWmfMaxBatchParams)
+      return set_error(kErrUnsupported, "%s: n_params=%lld (sum of nrows x width) above %d", fn, (long long)npar,
+                       kWmfMaxBatchParams);
+  }
+  m.G = p.G;
+  m.L = L;
   m.T_all = a->T_all;
   m.rank = a->rank;
   m.vtask_exp = a->vtask_exp != 0;
-  m.noise_off = 1 + a->dl;
-  m.f_off = m.noise_off + 1;
-  m.v_off = m.f_off + a->T_all * a->rank;
-  p.n_params = m.v_off + a->T_all;
+  m.noise_off = p.nrows[0] + p.nrows[1] * a->dl;
+  m.f_off = m.noise_off + p.nrows[2];
+  m.v_off = m.f_off + p.nrows[3] * a->T_all * a->rank;
+  p.n_params = (int)npar;
   p.lat = a->family == FGP_FAMILY_LATTICE;
   p.L = L;
   p.rn = rn;
   p.nbx = (int)((m.n[0] + kWG - 1) / kWG);
-  const size_t B = (size_t)a->B, d = (size_t)a->d, np = (size_t)m.np;
+  // every array G-fold (include/fgp_hip.h); G = 1: what one problem always had
+  const size_t G = (size_t)p.G, B = (size_t)a->B, d = (size_t)a->d, np = (size_t)m.np, GL = G * (size_t)L;
   size_t o = 0;
-  p.o_nat = o, o += wmf_align(8 * (1 + d));
-  p.o_gn = o, o += wmf_align(8 * (B + 1));
+  p.o_nat = o, o += wmf_align(8 * G * (1 + d));
+  p.o_gn = o, o += wmf_align(8 * (G * B + G));
   p.o_info = o, o += 256;
-  p.o_dsl = o, o += wmf_align(8 * np * (1 + d));
-  p.o_a = o, o += wmf_align(8 * (size_t)L);                              // k1, then u = dL/dk1
-  p.o_b = o, o += wmf_align((p.lat ? 16 : 8) * (size_t)L);               // lambda, then g~
-  p.o_w = o, o += p.lat ? wmf_align(16 * (size_t)L) : 0;                 // the lattice transforms' scratch
-  p.o_lams = o, o += wmf_align(16 * (size_t)L);
-  p.o_fac = o, o += wmf_align(16 * (size_t)L);
-  p.o_zinv = o, o += wmf_align(16 * (size_t)L);
-  p.o_glp = o, o += wmf_align(16 * (size_t)L);
-  p.o_z = o, o += wmf_align(16 * B * (size_t)rn);
-  p.o_ld = o, o += wmf_align(8 * (size_t)m.n[T - 1]);
-  p.o_part = o, o += wmf_align(8 * (np + 1) * 2 * (size_t)p.nbx);
-  p.o_pb = o, o += wmf_align(8 * (1 + d) * (size_t)p.nbx);               // fgp_wide_mt_k1_bwd's partials (G = 1)
+  p.o_dsl = o, o += wmf_align(8 * np * G * (1 + d));
+  p.o_a = o, o += wmf_align(8 * GL);                                     // k1, then u = dL/dk1
+  p.o_b = o, o += wmf_align((p.lat ? 16 : 8) * GL);                      // lambda, then g~
+  p.o_w = o, o += p.lat ? wmf_align(16 * GL) : 0;                        // the lattice transforms' scratch
+  p.o_lams = o, o += wmf_align(16 * GL);
+  p.o_fac = o, o += wmf_align(16 * GL);
+  p.o_zinv = o, o += wmf_align(16 * GL);
+  p.o_glp = o, o += wmf_align(16 * GL);
+  p.o_z = o, o += wmf_align(16 * G * B * (size_t)rn);
+  p.o_ld = o, o += wmf_align(8 * G * (size_t)m.n[T - 1]);
+  p.o_part = o, o += wmf_align(8 * G * (np + 1) * 2 * (size_t)p.nbx);
+  p.o_pb = o, o += wmf_align(8 * G * (1 + d) * (size_t)p.nbx);           // fgp_wide_mt_k1_bwd's partials
   p.pl_bytes = loss == FGP_LOSS_MLL ? 0 : 8 * (size_t)kWmfLossQ * (loss == FGP_LOSS_CV ? (size_t)T : 1) * (size_t)p.nbx;
   p.o_pl = o, o += wmf_align(p.pl_bytes);
+  p.sums_bytes = p.G > 1 ? 8 * G * (size_t)(2 + p.P1) : 0;
+  p.o_sums = o, o += wmf_align(p.sums_bytes);
   p.bytes = o;
   return kOk;
 }
@@ -571,8 +776,10 @@ struct WmfCtx {
   const fgp_wide_mt_fit_desc* a;
   const WmfPlan* p;
   WmfStep s;
+  WmfSums bs;                                      // G > 1: the totals kernel's and the step's arguments
+  WmfBStep bt;
   Switches sw;
-  double *nat, *gn, *dsl, *A, *logdet, *part, *pb, *pl;
+  double *nat, *gn, *dsl, *A, *logdet, *part, *pb, *pl, *sums;
   int* info;
   char* Bf;
   void* W;
@@ -619,6 +826,20 @@ static WmfCtx wmf_ctx(const fgp_wide_mt_fit_desc* a, const WmfPlan& p) {
   s.w = a->logdet_weight, s.lr = a->lr;
   s.part = c.part, s.dsl = c.dsl, s.nat = c.nat, s.gn = c.gn, s.info = c.info;
   s.loss = a->loss_metric, s.cv_weight = a->cv_weight, s.pl = c.pl;
+  c.sums = reinterpret_cast<double*>(w + p.o_sums);
+  if (p.G > 1) {
+    WmfSums& bs = c.bs;
+    bs.lay = p.lay;
+    bs.d = a->d, bs.dl = a->dl, bs.nbx = p.nbx;
+    bs.raw = a->raw, bs.rows = p.rows, bs.part = c.part, bs.dsl = c.dsl, bs.nat = c.nat, bs.sums = c.sums;
+    WmfBStep& bt = c.bt;
+    bt.f = s.f;
+    bt.G = p.G, bt.d = a->d, bt.dl = a->dl, bt.T_all = a->T_all, bt.rank = a->rank;
+    for (int q = 0; q < 5; ++q) bt.nrows[q] = p.nrows[q];
+    bt.rg_factor = a->rg_factor, bt.rg_vtask = a->rg_vtask;
+    bt.w = a->logdet_weight, bt.lr = a->lr;
+    bt.rows = p.rows, bt.sums = c.sums, bt.nat = c.nat, bt.gn = c.gn, bt.info = c.info;
+  }
   c.sw = read_switches();
   c.y = static_cast<const double2*>(a->y);
   return c;
@@ -644,79 +865,94 @@ static int wmf_stage(const WmfCtx& c, int iter, int stage, int mode, hipStream_t
   const fgp_wide_mt_fit_desc* a = c.a;
   const WmfPlan& p = *c.p;
   const WmfLay& m = p.lay;
-  const int T = m.T, np = m.np, d = a->d;
+  const int T = m.T, np = m.np, d = a->d, G = p.G;
   const fgp_mt_layout* lay = &a->layout;
   double *nat = c.nat, *A = c.A;
+  const int* rows = p.rows;
+  const int64_t nvec = (int64_t)G * a->B;          // data vectors: B of one problem, or one of each of G
   int rc = kOk;
   switch (stage) {
     case kWmsPrologue:
+      if (G > 1) {
+        k_wide_mt_fit_bstep<<<1, kWmfStepWG, 0, st>>>(c.bt, 0, 0, mode);
+        return check_launch("k_wide_mt_fit_bstep");
+      }
       k_wide_mt_fit_step<<<1, kWG, 0, st>>>(c.s, 0, 0, mode);
       return check_launch("k_wide_mt_fit_step");
     case kWmsK1:
-      // k1 of every pair into A at the pair's packed offset: the pairs that share k lie contiguously
+      // k1 of every pair into A, the pair's G rows together (pair-major: G offk[k] + (l - k) G n_k; one problem: the
+      // pair's packed offset): the pairs that share k lie contiguously
       for (int k = 0, q = 0; k < T && rc == kOk; ++k)
         for (int l = k; l < T && rc == kOk; ++l, ++q)
-          rc = fgp_wide_mt_k1(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
-                              A + m.offk[k] + (int64_t)(l - k) * m.n[k], st);
+          rc = fgp_wide_mt_k1(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + G, G,
+                              A + (int64_t)G * (m.offk[k] + (int64_t)(l - k) * m.n[k]), st);
       return rc;
     case kWmsForward:
-      // lambda = ft(k1), stable (AbstractFastGP.ft), the T - k rows of sorted task k in one call
+      // lambda = ft(k1), stable (AbstractFastGP.ft), the (T - k) G rows of sorted task k in one call
       for (int k = 0; k < T && rc == kOk; ++k) {
-        const int64_t n = m.n[k], rows = T - k;
+        const int64_t n = m.n[k], nr = (int64_t)(T - k) * G;
         const int lg = p.log2n[k];
-        double* in = A + m.offk[k];
-        void* out = c.Bf + c.esz * (size_t)m.offk[k];
-        if (!p.lat) rc = fgp_fwht(in, n, static_cast<double*>(out), rows, lg, 1, st);
-        else if (use_r2c(c.sw, true, lg)) rc = fgp_fftbr_real(in, n, out, c.W, rows, lg, st);
-        else rc = fgp_fftbr(in, n, 1, out, rows, lg, 1, st);
+        double* in = A + (int64_t)G * m.offk[k];
+        void* out = c.Bf + c.esz * (size_t)G * (size_t)m.offk[k];
+        if (!p.lat) rc = fgp_fwht(in, n, static_cast<double*>(out), nr, lg, 1, st);
+        else if (use_r2c(c.sw, true, lg)) rc = fgp_fftbr_real(in, n, out, c.W, nr, lg, st);
+        else rc = fgp_fftbr(in, n, 1, out, nr, lg, 1, st);
       }
       return rc;
     case kWmsLams: {
-      const dim3 gl((unsigned)p.nbx, (unsigned)np);
-      if (p.lat) k_wide_mt_lams<0><<<gl, kWG, 0, st>>>(m, a->raw, c.Bf, c.lams);
-      else k_wide_mt_lams<1><<<gl, kWG, 0, st>>>(m, a->raw, c.Bf, c.lams);
+      const dim3 gl((unsigned)p.nbx, (unsigned)np, (unsigned)G);
+      if (p.lat) k_wide_mt_lams<0><<<gl, kWG, 0, st>>>(m, a->raw, rows, c.Bf, c.lams);
+      else k_wide_mt_lams<1><<<gl, kWG, 0, st>>>(m, a->raw, rows, c.Bf, c.lams);
       return check_launch("k_wide_mt_lams");
     }
     case kWmsBlocks:
       // the structured factor, the solves of the B vectors, the selected inverse and dL/dlams (fgp_multitask.hip); a
       // non-positive pivot sets info and counts as log|pivot|, as in the generic loop and MtGeneralEngine
-      rc = fgp_mt_factor(lay, c.lams, 1, c.fac, c.logdet, c.info, st);
-      if (rc == kOk) rc = fgp_mt_solve(lay, c.fac, 1, c.y, p.rn, a->B, c.z, st);
-      if (rc == kOk) rc = fgp_mt_selinv(lay, c.fac, 1, c.zinv, st);
+      rc = fgp_mt_factor(lay, c.lams, G, c.fac, c.logdet, c.info, st);
+      if (rc == kOk) rc = fgp_mt_solve(lay, c.fac, G, c.y, p.rn, nvec, c.z, st);
+      if (rc == kOk) rc = fgp_mt_selinv(lay, c.fac, G, c.zinv, st);
       if (rc != kOk) return rc;
-      if (a->loss_metric == FGP_LOSS_MLL) return fgp_mt_mll_grad(lay, c.zinv, c.z, c.gn, c.gn + a->B, a->B, 1, c.glp, st);
+      if (a->loss_metric == FGP_LOSS_MLL) return fgp_mt_mll_grad(lay, c.zinv, c.z, c.gn, c.gn + nvec, nvec, G, c.glp, st);
       if (a->loss_metric == FGP_LOSS_CV) return p.lat ? wmf_loss_stage<0, true>(c, st) : wmf_loss_stage<1, true>(c, st);
       return p.lat ? wmf_loss_stage<0, false>(c, st) : wmf_loss_stage<1, false>(c, st);
     case kWmsContract: {
-      const dim3 gc((unsigned)p.nbx, (unsigned)np + 1);
+      const dim3 gc((unsigned)p.nbx, (unsigned)np + 1, (unsigned)G);
       if (p.lat)
-        k_wide_mt_contract<0><<<gc, kWG, 0, st>>>(m, a->raw, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet, p.nbx,
-                                                  c.part);
+        k_wide_mt_contract<0><<<gc, kWG, 0, st>>>(m, a->raw, rows, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet,
+                                                  p.nbx, c.part);
       else
-        k_wide_mt_contract<1><<<gc, kWG, 0, st>>>(m, a->raw, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet, p.nbx,
-                                                  c.part);
+        k_wide_mt_contract<1><<<gc, kWG, 0, st>>>(m, a->raw, rows, c.glp, c.Bf, c.y, c.z, (int64_t)a->B * p.rn, c.logdet,
+                                                  p.nbx, c.part);
       return check_launch("k_wide_mt_contract");
     }
     case kWmsAdjoint:
       // u = dL/dk1: the adjoint transform of g~ (lattice: the real part), batched as the forward
       for (int k = 0; k < T && rc == kOk; ++k) {
-        const int64_t n = m.n[k], rows = T - k;
+        const int64_t n = m.n[k], nr = (int64_t)(T - k) * G;
         const int lg = p.log2n[k];
-        double* out = A + m.offk[k];
-        void* in = c.Bf + c.esz * (size_t)m.offk[k];
-        if (!p.lat) rc = fgp_fwht(static_cast<const double*>(in), n, out, rows, lg, 1, st);
-        else if (use_r2c(c.sw, true, lg)) rc = fgp_ifftbr_real(in, n, nullptr, 0, out, n, c.W, rows, lg, st);
-        else rc = fgp_ifftbr(in, n, out, 1, c.W, rows, lg, 1, st);
+        double* out = A + (int64_t)G * m.offk[k];
+        void* in = c.Bf + c.esz * (size_t)G * (size_t)m.offk[k];
+        if (!p.lat) rc = fgp_fwht(static_cast<const double*>(in), n, out, nr, lg, 1, st);
+        else if (use_r2c(c.sw, true, lg)) rc = fgp_ifftbr_real(in, n, nullptr, 0, out, n, c.W, nr, lg, st);
+        else rc = fgp_ifftbr(in, n, out, 1, c.W, nr, lg, 1, st);
       }
       return rc;
     case kWmsK1Bwd:
+      // pair q's dscale [G], then dls [G][d]
       for (int k = 0, q = 0; k < T && rc == kOk; ++k)
         for (int l = k; l < T && rc == kOk; ++l, ++q)
-          rc = fgp_wide_mt_k1_bwd(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + 1, 1,
-                                  A + m.offk[k] + (int64_t)(l - k) * m.n[k], c.dsl + (int64_t)q * (1 + d),
-                                  c.dsl + (int64_t)q * (1 + d) + 1, c.pb, st);
+          rc = fgp_wide_mt_k1_bwd(a->pair[q].parts, m.n[k], d, a->pair[q].P, a->pair[q].ind, a->pair[q].cc, nat, nat + G, G,
+                                  A + (int64_t)G * (m.offk[k] + (int64_t)(l - k) * m.n[k]),
+                                  c.dsl + (int64_t)q * G * (1 + d), c.dsl + (int64_t)q * G * (1 + d) + G, c.pb, st);
       return rc;
     default:
+      if (G > 1) {
+        k_wide_mt_fit_sums<<<(unsigned)G, kWG, 0, st>>>(c.bs);
+        rc = check_launch("k_wide_mt_fit_sums");
+        if (rc != kOk) return rc;
+        k_wide_mt_fit_bstep<<<1, kWmfStepWG, 0, st>>>(c.bt, iter, mode, 0);
+        return check_launch("k_wide_mt_fit_bstep");
+      }
       k_wide_mt_fit_step<<<1, kWG, 0, st>>>(c.s, iter, mode, 0);
       return check_launch("k_wide_mt_fit_step");
   }
@@ -762,25 +998,20 @@ static int wmf_check(const char* fn, const fgp_wide_mt_fit_desc* desc, const Wmf
   return kOk;
 }
 
-}  // namespace fgp
-
-using namespace fgp;
-
-extern "C" {
-
-int fgp_wide_mt_fit_work(const fgp_wide_mt_fit_desc* desc, int64_t* bytes) {
+// The entry points, for one problem (bt NULL) and for a batch descriptor (a = &bt->one)
+static int wmf_api_work(const char* fn, const fgp_wide_mt_fit_desc* a, const fgp_wide_mt_fit_batch_desc* bt, int64_t* bytes) {
   WmfPlan p;
-  int rc = wmf_plan("fgp_wide_mt_fit_work", desc, p);
+  int rc = wmf_plan(fn, a, p, bt);
   if (rc != kOk) return rc;
-  if (!bytes) return set_error(kErrInvalid, "fgp_wide_mt_fit_work: null pointer: bytes");
+  if (!bytes) return set_error(kErrInvalid, "%s: null pointer: bytes", fn);
   *bytes = (int64_t)p.bytes;
   return kOk;
 }
 
-int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {
-  static const char* fn = "fgp_wide_mt_fit_run";
+static int wmf_api_run(const char* fn, const fgp_wide_mt_fit_desc* desc, const fgp_wide_mt_fit_batch_desc* bt, int iter0,
+                       int iters, int final_no_update, void* stream) {
   WmfPlan p;
-  int rc = wmf_plan(fn, desc, p);
+  int rc = wmf_plan(fn, desc, p, bt);
   if (rc != kOk) return rc;
   rc = wmf_check(fn, desc, p);
   if (rc != kOk) return rc;
@@ -792,31 +1023,22 @@ int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, 
   return wmf_run(desc, p, iter0, iters, final_no_update, (hipStream_t)stream);
 }
 
-int fgp_wide_mt_fit_work_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[15]) {
+static int wmf_api_work_layout(const char* fn, const fgp_wide_mt_fit_desc* a, const fgp_wide_mt_fit_batch_desc* bt,
+                               int64_t offsets[15]) {
   WmfPlan p;
-  int rc = wmf_plan("fgp_wide_mt_fit_work_layout", desc, p);
+  int rc = wmf_plan(fn, a, p, bt);
   if (rc != kOk) return rc;
-  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_work_layout: null pointer: offsets");
+  if (!offsets) return set_error(kErrInvalid, "%s: null pointer: offsets", fn);
   const size_t o[15] = {p.o_nat,  p.o_gn,   p.o_info, p.o_dsl, p.o_a,  p.o_b,    p.o_w, p.o_lams,
                         p.o_fac, p.o_zinv, p.o_glp,  p.o_z,   p.o_ld, p.o_part, p.o_pb};
   for (int i = 0; i < 15; ++i) offsets[i] = (int64_t)o[i];
   return kOk;
 }
 
-int fgp_wide_mt_fit_loss_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[2]) {
+static int wmf_api_stage(const char* fn, const fgp_wide_mt_fit_desc* desc, const fgp_wide_mt_fit_batch_desc* bt, int iter,
+                         int stage, int mode, void* stream) {
   WmfPlan p;
-  int rc = wmf_plan("fgp_wide_mt_fit_loss_layout", desc, p);
-  if (rc != kOk) return rc;
-  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_loss_layout: null pointer: offsets");
-  offsets[0] = (int64_t)p.o_pl;
-  offsets[1] = (int64_t)p.pl_bytes;
-  return kOk;
-}
-
-int fgp_wide_mt_fit_stage(const fgp_wide_mt_fit_desc* desc, int iter, int stage, int mode, void* stream) {
-  static const char* fn = "fgp_wide_mt_fit_stage";
-  WmfPlan p;
-  int rc = wmf_plan(fn, desc, p);
+  int rc = wmf_plan(fn, desc, p, bt);
   if (rc != kOk) return rc;
   rc = wmf_check(fn, desc, p);
   if (rc != kOk) return rc;
@@ -835,5 +1057,75 @@ int fgp_wide_mt_fit_stage(const fgp_wide_mt_fit_desc* desc, int iter, int stage,
   const WmfCtx c = wmf_ctx(desc, p);
   return wmf_stage(c, iter, stage, mode, (hipStream_t)stream);
 }
+
+}  // namespace fgp
+
+using namespace fgp;
+
+extern "C" {
+
+int fgp_wide_mt_fit_work(const fgp_wide_mt_fit_desc* desc, int64_t* bytes) {
+  return wmf_api_work("fgp_wide_mt_fit_work", desc, nullptr, bytes);
+}
+
+int fgp_wide_mt_fit_run(const fgp_wide_mt_fit_desc* desc, int iter0, int iters, int final_no_update, void* stream) {
+  return wmf_api_run("fgp_wide_mt_fit_run", desc, nullptr, iter0, iters, final_no_update, stream);
+}
+
+int fgp_wide_mt_fit_work_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[15]) {
+  return wmf_api_work_layout("fgp_wide_mt_fit_work_layout", desc, nullptr, offsets);
+}
+
+int fgp_wide_mt_fit_loss_layout(const fgp_wide_mt_fit_desc* desc, int64_t offsets[2]) {
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_loss_layout", desc, p);
+  if (rc != kOk) return rc;
+  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_loss_layout: null pointer: offsets");
+  offsets[0] = (int64_t)p.o_pl;
+  offsets[1] = (int64_t)p.pl_bytes;
+  return kOk;
+}
+
+int fgp_wide_mt_fit_stage(const fgp_wide_mt_fit_desc* desc, int iter, int stage, int mode, void* stream) {
+  return wmf_api_stage("fgp_wide_mt_fit_stage", desc, nullptr, iter, stage, mode, stream);
+}
+
+// ---- the batch descriptor's counterparts
+#define WMF_BATCH_ONE(fn)                                                        \
+  if (!desc) return set_error(kErrInvalid, "%s: null pointer: desc", fn);       \
+  const fgp_wide_mt_fit_desc* one = &desc->one
+
+int fgp_wide_mt_fit_batch_work(const fgp_wide_mt_fit_batch_desc* desc, int64_t* bytes) {
+  WMF_BATCH_ONE("fgp_wide_mt_fit_batch_work");
+  return wmf_api_work("fgp_wide_mt_fit_batch_work", one, desc, bytes);
+}
+
+int fgp_wide_mt_fit_batch_run(const fgp_wide_mt_fit_batch_desc* desc, int iter0, int iters, int final_no_update,
+                              void* stream) {
+  WMF_BATCH_ONE("fgp_wide_mt_fit_batch_run");
+  return wmf_api_run("fgp_wide_mt_fit_batch_run", one, desc, iter0, iters, final_no_update, stream);
+}
+
+int fgp_wide_mt_fit_batch_work_layout(const fgp_wide_mt_fit_batch_desc* desc, int64_t offsets[15]) {
+  WMF_BATCH_ONE("fgp_wide_mt_fit_batch_work_layout");
+  return wmf_api_work_layout("fgp_wide_mt_fit_batch_work_layout", one, desc, offsets);
+}
+
+int fgp_wide_mt_fit_batch_stage(const fgp_wide_mt_fit_batch_desc* desc, int iter, int stage, int mode, void* stream) {
+  WMF_BATCH_ONE("fgp_wide_mt_fit_batch_stage");
+  return wmf_api_stage("fgp_wide_mt_fit_batch_stage", one, desc, iter, stage, mode, stream);
+}
+
+int fgp_wide_mt_fit_batch_layout(const fgp_wide_mt_fit_batch_desc* desc, int64_t offsets[2]) {
+  WMF_BATCH_ONE("fgp_wide_mt_fit_batch_layout");
+  WmfPlan p;
+  int rc = wmf_plan("fgp_wide_mt_fit_batch_layout", one, p, desc);
+  if (rc != kOk) return rc;
+  if (!offsets) return set_error(kErrInvalid, "fgp_wide_mt_fit_batch_layout: null pointer: offsets");
+  offsets[0] = (int64_t)p.o_sums;
+  offsets[1] = (int64_t)p.sums_bytes;
+  return kOk;
+}
+#undef WMF_BATCH_ONE
 
 }  // extern "C"

@@ -465,6 +465,32 @@ class MultiTaskFastGP(AbstractFastGP):
             return False
         return all(self._wide_pair_spec(min(a, b), max(a, b)) is not None for a in act for b in act)
 
+    def _mt_wide_batch_ok(self):
+        """The device-resident MLL fit at 9 <= d <= 64 with PARAMETER batches (fgp_wide_mt_fit_batch_desc:
+        WideMtEngine over G = d_out problems, opt-in by FGP_WIDE_MT_FIT_BATCH=1): _mt_wide_ok's conditions with "no
+        parameter batch" replaced by _mt_param_rows giving rows, the trailing shapes of _mt_general_ok, at most 4096
+        outputs and 8192 raw elements."""
+        if not ops._wide(self.d) or self.d > N.WIDE_MAX_D or not ops.wide_fused():
+            return False
+        act = [l for l in range(self.num_tasks) if self._ns[l] > 0]
+        if not act or len(act) > N.MT_MAX_TASKS or self.adaptive_nugget:
+            return False
+        if any(self._tfs[k][1] is not _exp for k in ("scale", "lengthscales", "noise")):
+            return False
+        if self.tf_factor_task_kernel is not _identity or self.tf_noise_task_kernel not in (_exp, _identity):
+            return False
+        T = self.num_tasks
+        if self.raw_scale.shape[-1] != 1 or self.raw_noise.shape[-1] != 1 or \
+                self.raw_lengthscales.shape[-1] not in (1, self.d) or self.raw_factor_task_kernel.dim() < 2 or \
+                self.raw_factor_task_kernel.shape[-2] != T or self.raw_noise_task_kernel.shape[-1] != T:
+            return False
+        pr = self._mt_param_rows()
+        if pr is None or pr is False:
+            return False
+        if len(pr[0][0]) > 4096 or sum(n * w for n, w in zip(pr[1], self._mt_row_widths())) > 8192:
+            return False
+        return all(self._wide_pair_spec(min(a, b), max(a, b)) is not None for a in act for b in act)
+
     def _mt_wide_alt_ok(self):
         """fit(loss_metric="GCV" / "CV") at 9 <= d <= 64 on the device (fgp_wide_mt_fit_desc.loss_metric): under
         FGP_WIDE_FIT_DEVICE=1, _mt_wide_ok's domain with the same n > 0 in every task (the closed forms of T tasks of
@@ -902,7 +928,7 @@ class MultiTaskFastGP(AbstractFastGP):
 
     def _device_fit_args(self, loss_metric, optimizer, masks, cv_weights):
         """The MLL on the device inside _mt_fused_ok or _mt_general_ok, or inside _mt_wide_ok under
-        FGP_WIDE_FIT_DEVICE=1; GCV / CV of T tasks with equal n and a fixed or
+        FGP_WIDE_FIT_DEVICE=1, or inside _mt_wide_batch_ok under FGP_WIDE_MT_FIT_BATCH=1; GCV / CV of T tasks with equal n and a fixed or
         a learned task kernel (k_mt_spec_iter's GCV / CV variants + k_spec_loss_step, ABI 17 / 18; util.py:371-394,
         abstract_gp.py:242-272), or at 9 <= d <= 64 inside _mt_wide_alt_ok (fgp_wide_mt_fit_desc.loss_metric), unless
         FGP_ALT_LOSS_DEVICE=0."""
@@ -913,6 +939,8 @@ class MultiTaskFastGP(AbstractFastGP):
                 return {}
             # 9 <= d <= 64: opt-in, the switch of a single wide GP's fit (default: the generic autograd loop)
             wide = os.environ.get("FGP_WIDE_FIT_DEVICE", "0")[:1] == "1" and self._mt_wide_ok()
+            # ... and with a parameter batch under a switch of its own (GCV / CV of a batch keep the generic loop)
+            wide = wide or (os.environ.get("FGP_WIDE_MT_FIT_BATCH", "0")[:1] == "1" and self._mt_wide_batch_ok())
             return {} if wide else None
         ok = (self._mt_fused_ok() or self._mt_learn_ok() or self._mt_wide_alt_ok()) and \
             os.environ.get("FGP_ALT_LOSS_DEVICE", "1")[:1] != "0"
@@ -1395,10 +1423,25 @@ class WideMtEngine(MtGeneralEngine):
         Y = lo.pack([gp.get_ytilde(l).to(torch.complex128) for l in range(T)])
         B = int(np.prod(tuple(Y.shape[:-1]))) if Y.dim() > 1 else 1
         self.y = Y.reshape(B, -1).resolve_conj().contiguous()
-        self.G, self.B, self.rows = 1, B, None
+        # parameter batches (as MtGeneralEngine): every output its own problem, G = d_out with one data vector each, its
+        # parameters the rows of _mt_param_rows -- range-checked here, the C side cannot follow the device array
+        pr = gp._mt_param_rows()
+        G = 1 if pr is None else B
+        if G > 1:
+            if loss_metric != "MLL":
+                raise ValueError("a parameter batch fits the MLL on the device")
+            B = 1
+            rows_h, nrows = np.ascontiguousarray(pr[0], dtype=np.int32), [int(v) for v in pr[1]]
+            if rows_h.shape != (5, G) or any(rows_h[q].min() < 0 or rows_h[q].max() >= nrows[q] for q in range(5)):
+                raise ValueError("parameter rows outside their blocks")
+            self.rows = torch.from_numpy(rows_h).to(dev)
+        else:
+            self.rows = None
+            nrows = [1] * 5
+        self.G, self.B = G, B
         dl = int(gp.raw_lengthscales.shape[-1])
         r = int(gp.raw_factor_task_kernel.shape[-1])
-        self.sizes = gp._mt_row_widths()
+        self.sizes = tuple(n * w for n, w in zip(nrows, gp._mt_row_widths()))
         self.raw = torch.cat([gp.raw_scale.detach().reshape(-1), gp.raw_lengthscales.detach().reshape(-1),
                               gp.raw_noise.detach().reshape(-1), gp.raw_factor_task_kernel.detach().reshape(-1),
                               gp.raw_noise_task_kernel.detach().reshape(-1)]).to(dev, torch.float64).contiguous()
@@ -1406,7 +1449,11 @@ class WideMtEngine(MtGeneralEngine):
         st = torch.zeros((3, self.n_params), dtype=torch.float64, device=dev)
         self.prev, self.step, self.grad = st[0], st[1], st[2]
         d_out = int(torch.tensor(tuple(gp.shape_batch)).prod()) if len(gp.shape_batch) else 1
-        desc = N.WideMtFitDesc()
+        # a parameter batch: fgp_wide_mt_fit_batch_desc = the one-problem descriptor (filled below through `desc`, a view
+        # of its first member) followed by G / rows / nrows, with entry points of its own
+        self._bdesc = N.WideMtFitBatchDesc() if G > 1 else None
+        desc = self._bdesc.one if G > 1 else N.WideMtFitDesc()
+        self._entry = "fgp_wide_mt_fit_batch_" if G > 1 else "fgp_wide_mt_fit_"
         desc.family, desc.d, desc.B = int(gp._FAMILY), int(d), B
         desc.layout = lo.lay
         for k, a in enumerate(lo.active):
@@ -1437,13 +1484,19 @@ class WideMtEngine(MtGeneralEngine):
         desc.eta_minus, desc.eta_plus = RPROP_ETAS
         desc.step_min, desc.step_max = RPROP_STEPS
         # one problem's logdet stands for the d_out outputs sharing it (abstract_gp.py:256); the loss is
-        # 1/2 (norm + w logdet) + 1/2 d_out sum(n) log(2 pi)
-        desc.logdet_weight = float(d_out)
+        # 1/2 (norm + w logdet) + 1/2 d_out sum(n) log(2 pi).  With a parameter batch every output is its own problem
+        # (weight 1, as MtGeneralEngine)
+        desc.logdet_weight = 1.0 if G > 1 else float(d_out)
+        if G > 1:
+            self._bdesc.G = G
+            self._bdesc.rows = self.rows.data_ptr()
+            for q in range(5):
+                self._bdesc.nrows[q] = nrows[q]
         desc.mll_const = 0.5 * float(mll_constant(d_out, sum(gp._ns)))
         desc.loss_metric = {"MLL": N.LOSS_MLL, "GCV": N.LOSS_GCV, "CV": N.LOSS_CV}[loss_metric]
         desc.cv_weight = float(cv_weight)
         wb = ctypes.c_int64(0)
-        N.call("fgp_wide_mt_fit_work", desc, ctypes.byref(wb))
+        N.call(self._entry + "work", self._bdesc if G > 1 else desc, ctypes.byref(wb))
         self.work = torch.empty((max(1, wb.value),), dtype=torch.uint8, device=dev)
         desc.work = self.work.data_ptr()
         self.desc = desc
@@ -1453,5 +1506,5 @@ class WideMtEngine(MtGeneralEngine):
         """Enqueue `iters` iterations writing history rows iter0 .. iter0 + iters - 1 (plain launches on the current
         stream, no host synchronisation).  iter0 = 0 starts a new fit (Rprop state reset on the device)."""
         self.ensure_history(iter0 + iters)
-        N.call("fgp_wide_mt_fit_run", self.desc, int(iter0), int(iters), int(bool(final_no_update)),
-               N.stream_ptr(self.device))
+        N.call(self._entry + "run", self._bdesc if self.G > 1 else self.desc, int(iter0), int(iters),
+               int(bool(final_no_update)), N.stream_ptr(self.device))

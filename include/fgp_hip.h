@@ -996,6 +996,60 @@ extern int (fgp_wide_mt_fit_stage)(const fgp_wide_mt_fit_desc* desc, int iter, i
  * rounded up to 256 = fgp_wide_mt_fit_work's bytes, and an MLL desc's bytes and 15 offsets are what they were.  Under
  * GCV / CV stage 4 of fgp_wide_mt_fit_stage is factor, solve, selected inverse, sums, gradient. */
 extern int (fgp_wide_mt_fit_loss_layout)(const fgp_wide_mt_fit_desc* desc, int64_t offsets[2]);
+/* Addition to ABI 20 -- PARAMETER batches of the wide multitask fit loop.  fgp_wide_mt_fit_desc keeps its layout (its
+ * callers and its mirror are untouched); the batch descriptor is that descriptor followed by fgp_mt_fit_desc's ABI 16
+ * fields with their semantics, and has entry points of its own, each the counterpart of the one-problem one:
+ *   G problems (0 = 1), problem g's parameters row rows[q * G + g] of parameter block q (scale, lengthscales, noise, task
+ *   factor, task noise; DEVICE int array [5][G], which this side cannot follow: the caller checks every entry against
+ *   nrows; NULL: every problem row 0) of nrows[q] rows (0 = 1).  raw = [scale rows, lengthscale rows (dl each), noise
+ *   rows, task-factor rows (T_all x rank each), task-noise rows (T_all each)], n_params = sum_q nrows[q] width[q].  The
+ *   loss is the sum over the problems; a row shared by several problems receives the sum of their gradients; Rprop runs
+ *   per raw element.
+ * For G > 1: one.B must be 1 (one.y is [G][R nmin], one data vector per problem) and one.loss_metric FGP_LOSS_MLL (both
+ * else FGP_ERR_UNSUPPORTED); G <= 4096 and n_params <= 8192 (else FGP_ERR_UNSUPPORTED); G < 0, a negative nrows entry, or
+ * more than one row of a block with G <= 1 is FGP_ERR_INVALID; all before any HIP call, the field named.  With G <= 1 the
+ * batch entry points run what fgp_wide_mt_fit_run runs on `one`: the same kernels, work bytes, offsets and bits.
+ * The launch count does not depend on G: 3 np + 2 T + 8 calls per iteration, one more than one problem's (the totals
+ * kernel), and no host synchronisation.  The arrays of `work` (fgp_wide_mt_fit_batch_work_layout's 15 offsets, those of
+ * fgp_wide_mt_fit_work_layout G-fold):
+ *   nat    scale [G], then lengthscales [G][d]: each problem's natural row, gathered through rows (fgp_wide_mt_k1 takes
+ *          the scales and the lengthscale rows as two contiguous arrays; at G = 1 this is [1 + d])
+ *   gn     [G] = 1/2, then gl [G] = 1/2 w (fgp_mt_mll_grad's grad_norm / grad_logdet; vector b belongs to problem b mod G)
+ *   dsl    per pair dscale [G], then dls [G][d]
+ *   A, B   (k1 / u, lambda / g~) pair-major [p][G][n_k]: fgp_wide_mt_k1(.., G, ..) writes a pair's G rows contiguously
+ *          and the T - k pairs of sorted task k stay ONE batched transform call of (T - k) G rows; pair (k, l)'s row of
+ *          problem g starts at element G offk + ((l - k) G + g) n_k
+ *   W      the lattice transforms' scratch, 16 G L bytes
+ *   lams, fac, zinv, glp   problem-major [G][L], what fgp_mt_factor / _solve / _selinv / _mll_grad take
+ *   z [G][R nmin], logdet [G][nmin], part [G][np + 1][2][nbx], pb fgp_wide_mt_k1_bwd_work(n_0, d, 1, G) doubles
+ *   sums   [G][2 + P1], P1 = 2 + dl + T_all rank + T_all, after the GCV / CV partials' (empty) place
+ * k_wide_mt_lams and k_wide_mt_contract take the problem as blockIdx.z and read its noise, factor and task-noise rows
+ * through rows; per problem the arithmetic is one problem's, operation for operation.  k_wide_mt_fit_sums (one workgroup
+ * per problem) is the evaluation half of the one-problem step: the second level of the problem's partials, its dsl
+ * summed over the pairs, and its raw-space contribution to each of its own P1 parameters, sums[g] = (norm_g, logdet_g,
+ * those P1 values in one problem's raw order).  The step (one workgroup) gives raw element x the sum of sums[g][x's
+ * column] over the problems g whose row it is, g ascending from 0.0; the loss row is (1/2 (sum_g norm_g + w sum_g
+ * logdet_g) + mll_const, sum_g norm_g, w sum_g logdet_g), g ascending; then the history rows, grad_out, rprop_update by
+ * the block's rg_*, and the natural rows of the new parameters.
+ * Contract: problem g's slices of every work array through stage 7 carry the bits of a fgp_wide_mt_fit_run of that
+ * problem alone, its rows gathered into a one-problem raw vector; sums[g] carries the bits of that run's (loss_hist[1],
+ * loss_hist[2] / w, grad_out); so an unshared row's gradient and Rprop step carry the bits of that run.
+ * fgp_wide_mt_fit_batch_work / _run / _work_layout / _stage: as fgp_wide_mt_fit_work / _run / _work_layout / _stage (stage 8
+ * is the totals kernel and the step).  fgp_wide_mt_fit_batch_layout -- test hook, read-only, no HIP call: offsets[0] = the
+ * BYTE offset into `work` of sums, offsets[1] = their length in bytes (0 when G <= 1); offsets[0] + offsets[1] rounded up
+ * to 256 = fgp_wide_mt_fit_batch_work's bytes. */
+typedef struct fgp_wide_mt_fit_batch_desc {
+  fgp_wide_mt_fit_desc one;           /* the problem every g shares: layout, pairs, y, raw, Rprop, histories, work */
+  int G;            /* problems; 0 = 1 */
+  const int* rows;  /* device [5][G]; NULL: every problem row 0 */
+  int nrows[5];     /* rows per block; 0 = 1 */
+} fgp_wide_mt_fit_batch_desc;
+extern int (fgp_wide_mt_fit_batch_work)(const fgp_wide_mt_fit_batch_desc* desc, int64_t* bytes);
+extern int (fgp_wide_mt_fit_batch_run)(const fgp_wide_mt_fit_batch_desc* desc, int iter0, int iters, int final_no_update,
+                                       void* stream);
+extern int (fgp_wide_mt_fit_batch_work_layout)(const fgp_wide_mt_fit_batch_desc* desc, int64_t offsets[15]);
+extern int (fgp_wide_mt_fit_batch_stage)(const fgp_wide_mt_fit_batch_desc* desc, int iter, int stage, int mode, void* stream);
+extern int (fgp_wide_mt_fit_batch_layout)(const fgp_wide_mt_fit_batch_desc* desc, int64_t offsets[2]);
 
 /* ABI 15 -- consistency check of the fused spectral fit's last-arriver hand-off (a test hook, no reference
  * counterpart).  enable != 0 arms it for the following fgp_fit_run calls: every wave of the one-launch
